@@ -27,6 +27,12 @@ GPU and built inside the run by our own GPU builder (cf_build_index; byte-identi
 centrifuge-build, tests/test_gpu_build.py).  Config 2's uids start with "cid" like p_compressed's, so the index is
 `compressed()` (bt2_idx.h:648-663) and the classifier runs with ihits = 20 as it does on the real one.  Index
 construction is outside the timed path.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K resident steps and prints the line (`value`,
+`ms_per_step`, the timed steps' own kernel times and op counts).  Everything else — the host-to-host leg, one slot alone through
+the blocking calls, the measured random-read rate, the CPU reference and its parity check, the per-rank report merge, the
+command line's end-to-end run and the other presets — runs only under `--full`.  `--dump-outputs DIR` writes what the last timed
+step returned (a fixed, seeded sample of its per-query columns and of those queries' rows, float64) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -594,7 +600,7 @@ def run_other_configs(presets, steps, budget_s):
         #  workload prints — where a read prints more than 1.25 rows, a slot's first batch fetches the rest synchronously into a
         #  re-allocated pinned buffer and its second re-allocates once more for the margin; with 2 warm-up steps for 3 slots all
         #  of that fell into the 8 timed steps of the repeat-rich preset: 27-30 ms per step instead of 19.9)
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--steps", str(steps), "--warmup", "6", "--other-configs", "",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", c, "--steps", str(steps), "--warmup", "6", "--other-configs", "",
                "--cpu-sample", os.environ.get("CF_BENCH_OTHER_CPU_SAMPLE", "200000")]
         if budget_gb is not None:
             cmd += ["--hbm-budget-gb", str(budget_gb)]
@@ -636,6 +642,42 @@ def run_other_configs(presets, steps, budget_s):
         except Exception as e:
             out[key] = {"failed": repr(e), "wall_s": time.time() - t0}
     return out
+
+
+DUMP_QUERIES, DUMP_ROWS = 1 << 18, 1 << 20      # at most 3 x 2 + 5 x 8 MB of float64 = 46 MB
+
+
+def sample_outputs(res, narrow):
+    """What a caller of the timed path receives from one step (wait_narrow / wait), cut to a fixed, seeded sample: the per-query
+    columns at DUMP_QUERIES query indices (numpy seed 0, sorted) and the rows of those queries, in order, up to DUMP_ROWS.
+    -> {name: float64 array} (every field is an unsigned integer below 2**53, so float64 holds it exactly)"""
+    if narrow:
+        rows, qinfo, score2, _ = res
+        per_query = {"qinfo": qinfo, "score2": score2}
+        n_rows = (qinfo & 0x3F).astype(np.int64)
+    else:
+        rows, _, n_rows_, score2, max_score, _ = res
+        per_query = {"n_rows": n_rows_, "score2": score2, "max_score": max_score}
+        n_rows = n_rows_.astype(np.int64)
+    nq = len(n_rows)
+    q = np.arange(nq) if nq <= DUMP_QUERIES else np.sort(np.random.default_rng(0).choice(nq, DUMP_QUERIES, replace=False))
+    first = np.zeros(nq + 1, dtype=np.int64)
+    np.cumsum(n_rows, out=first[1:])
+    cnt = n_rows[q]
+    idx = np.repeat(first[q], cnt) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    idx = idx[:DUMP_ROWS]
+    out = {"query_index": q.astype(np.float64)}
+    out.update({k: v[q].astype(np.float64) for k, v in per_query.items()})
+    sel = rows[idx]
+    out.update({"row_" + f: sel[f].astype(np.float64) for f in rows.dtype.names})
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    log("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(arrays), sum(v.nbytes for v in arrays.values()) / 1e6, d))
 
 
 PRESETS = {
@@ -692,6 +734,11 @@ def main():
     ap.add_argument("--other-steps", type=int, default=int(os.environ.get("CF_BENCH_OTHER_STEPS", 20)))
     ap.add_argument("--other-budget-s", type=float, default=float(os.environ.get("CF_BENCH_OTHER_BUDGET_S", 1300)),
                     help="wall-clock budget of all other_configs runs together (a preset that would not fit is skipped and says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: host-to-host leg, one slot alone, random-read rate, CPU reference + parity, "
+                         "report merge, end-to-end command line, other presets (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (a fixed, seeded sample) as DIR/<name>.npy")
     a = ap.parse_args()
     P = dict(PRESETS[a.config])
     if a.small_range_rows is not None:
@@ -907,14 +954,16 @@ def main():
     torch.cuda.synchronize()
     # ---- ... then the PCIe-inclusive rate (never `value`: reported as host_to_host): packed reads in pinned host memory -> H2D ->
     # plan + kernels -> D2H -> rows in pinned host memory, S batches in flight, the same K steps
-    if dist is not None:
-        dist.barrier()
-    t0 = time.perf_counter()
-    pipeline(a.steps)
-    torch.cuda.synchronize()
-    if dist is not None:
-        dist.barrier()                         # (every rank has finished its K steps: the slowest rank's time, as for `value`)
-    h2h_dt = time.perf_counter() - t0
+    h2h_dt = None
+    if a.full:
+        if dist is not None:
+            dist.barrier()
+        t0 = time.perf_counter()
+        pipeline(a.steps)
+        torch.cuda.synchronize()
+        if dist is not None:
+            dist.barrier()                     # (every rank has finished its K steps: the slowest rank's time, as for `value`)
+        h2h_dt = time.perf_counter() - t0
     # ---- the timed region of `value`: the inputs are resident in HBM when it starts (every slot holds its read set since the
     # steps above); a step = plan + every kernel of a batch + its rows downloaded into pinned host memory
     pipeline(min(a.warmup, S), resident=True)
@@ -934,12 +983,15 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0 and a.steps > 0:
+        dumped = sample_outputs(last[(a.steps - 1) % S], narrow)      # (views of pinned memory: taken before anything reuses the slot)
     per_rank_ms = [dt / max(1, a.steps) * 1e3]
     if dist is not None:                       # MAX over ranks is the step time; every rank's own time shows a straggler
         times = cfd.per_rank(dist, dt, rank, world)
         per_rank_ms = [x / max(1, a.steps) * 1e3 for x in times]
         dt = max(times)
-        h2h_dt = max(cfd.per_rank(dist, h2h_dt, rank, world))
+        if h2h_dt is not None:
+            h2h_dt = max(cfd.per_rank(dist, h2h_dt, rank, world))
         index_open_all = cfd.per_rank(dist, index_open_s, rank, world)
     else:
         index_open_all = [index_open_s]
@@ -953,28 +1005,35 @@ def main():
     if last[0] is None:                                   # --steps 0 --warmup 0: still give slot 0 a batch
         submit_set(0)
         last[0] = slots[0].wait_narrow(copy=False) if narrow else slots[0].wait(copy=False, offsets=False)
-    reps, iso = 3, np.zeros(6)
-    t1 = time.perf_counter()
-    for _ in range(reps):
-        iso[5] += slots[0].plan(st_k.cuda_stream)
-        slots[0].classify(st_k.cuda_stream)
-        iso[:5] += np.array(slots[0].timings()[0])
-    resident_wall = (time.perf_counter() - t1) / reps
-    iso /= reps
-    if acc["n"] == 0:
-        kms, plan_step_ms = iso[:5], iso[5]
+    iso, resident_wall = None, None
+    if a.full or acc["n"] == 0:
+        reps, iso = 3, np.zeros(6)
+        t1 = time.perf_counter()
+        for _ in range(reps):
+            iso[5] += slots[0].plan(st_k.cuda_stream)
+            slots[0].classify(st_k.cuda_stream)
+            iso[:5] += np.array(slots[0].timings()[0])
+        resident_wall = (time.perf_counter() - t1) / reps
+        iso /= reps
+        if acc["n"] == 0:
+            kms, plan_step_ms = iso[:5], iso[5]
     ops = slots[0].opcounts()
-    if narrow:                                             # rows of read set 0 (the parity sample lives there), in the wide form
-        rows_, n_rows_, s2_, ms_, info_ = slots[0].wait_narrow(expand=(None, read_len, paired))
-        first_ = np.zeros(len(n_rows_) + 1, dtype=np.uint64)
-        np.cumsum(n_rows_, out=first_[1:])
-        res0 = (rows_, first_, n_rows_, s2_, ms_, info_)
-    else:
-        res0 = slots[0].wait(copy=False)
+    res0 = None
+    if a.full:
+        if narrow:                                         # rows of read set 0 (the parity sample lives there), in the wide form
+            rows_, n_rows_, s2_, ms_, info_ = slots[0].wait_narrow(expand=(None, read_len, paired))
+            first_ = np.zeros(len(n_rows_) + 1, dtype=np.uint64)
+            np.cumsum(n_rows_, out=first_[1:])
+            res0 = (rows_, first_, n_rows_, s2_, ms_, info_)
+        else:
+            res0 = slots[0].wait(copy=False)
+        printed0, info0 = len(res0[0]), res0[5]
+    else:                                                  # slot 0's last timed batch (read set 0): its rows as they came down
+        printed0, info0 = len(last[0][0]), last[0][3 if narrow else 5]
 
     # ---- N > 1: the per-rank report images meet on rank 0 (observed tuples for the EM); outside the timed region
     merged_rows = None
-    if dist is not None:
+    if dist is not None and a.full:
         rep = capi.Report(ix)
         rows, first, n_rows, score2, max_score, info = res0
         rep.add(rows, n_rows, max_score, 0)
@@ -1003,15 +1062,15 @@ def main():
         # resolve-table / SA-sample entry and a 16-byte reference record per resolved row, the LF steps of the walk, the printed
         # rows (24 bytes) and three words per query out — a superset of the search's figure by construction
         whole_bytes = search_bytes + 16 * calls + (ix.sa_width + 16) * ops.n_rows + (64 if planes else 128) * ops.n_walk + \
-            24 * len(res0[0]) + 12 * nq_all
-        rand_gbps = ix.random_read_gbps(1 << 26, 64)
+            24 * printed0 + 12 * nq_all
+        rand_gbps = ix.random_read_gbps(1 << 26, 64) if a.full else None
         if narrow:
             pcie_in = n_reads * ((read_len + 3) // 4 + 4) + 12 * len(sets[0][4][0].a)
-            pcie_out = len(res0[0]) * 16 + nq_all * 5
+            pcie_out = printed0 * 16 + nq_all * 5
         else:
             pcie_in = n_reads * (W * 8 + 8) + (n_reads * W * 4 if a.dense_nmask else 12 * len(sets[0][4][0].a))
-            pcie_out = len(res0[0]) * 24 + nq_all * 12
-        rows_out = int(res0[5]["planned_sa_rows"])
+            pcie_out = printed0 * 24 + nq_all * 12
+        rows_out = int(info0["planned_sa_rows"])
         res = {
             "metric": "classified reads/sec (whole node) on 100bp synthetic reads vs p_compressed; HBM GB/s achieved",
             "value": value, "unit": "reads/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -1029,21 +1088,11 @@ def main():
                        "text_verify_sample_every_nth": (1 << tv_rate) if tv_rate >= 0 else None, "text_verify_build_ms": tv_ms, "wide_ftab_chars": ix.L.cf_index_wide_ftab_chars(ix.h), "occ_planes": planes, "occ_planes_build_ms": ix.L.cf_index_occ_planes_build_ms(ix.h), "pair_planes": bool(ix_cfg["pair_planes"]),
                        "hbm_budget_gb": a.hbm_budget_gb or None, "hbm_offered_gb": budget / 1e9, "index_options": P.get("index_opts") or None, "small_range_rows_in_effect": int(ix_cfg.get("small_range_rows", 0)), "repeat_fraction": ix_cfg.get("repeat_fraction"), "plan_realised": ix_cfg.get("plan_realised"),
                        "host_link": host_link(torch, local),
-                       "host_to_host_reads_per_s": n_reads * world * a.steps / h2h_dt, "host_to_host_ms_per_step": h2h_dt / max(1, a.steps) * 1e3,
                        "read_sets": "%d distinct read sets (one per slot, seeded apart): step i classifies set i %% %d again — throughput is that of fresh reads (no result is cached), but the sets' own lines may still sit in L2 / MALL from three steps before" % (S, S),
                        "index_tables": {k_: ix_cfg[k_] for k_ in ("file_section_bytes", "wide_ftab_bytes", "text_bytes", "planes_bytes", "pair_planes_bytes", "resolve_bytes", "total_bytes", "est_requests_per_100bp_read")},
                        "parallelism": "index replicated per GPU, reads sharded, RCCL all-reduce of per-taxon counters"},
             "per_rank_ms_per_step": per_rank_ms,
             "timing_scope": "inputs resident in HBM when the timed region starts (packed reads uploaded by the warm-up steps): plan/search/post/walk/score/compact -> D2H -> rows in pinned host memory; K steps over S slots in flight",
-            "host_to_host": {"reads_per_s": n_reads * world * a.steps / h2h_dt, "ms_per_step": h2h_dt / max(1, a.steps) * 1e3,
-                             "note": "the PCIe-inclusive rate (SURVEY 8d's scope, rounds 1-3's `value`): pinned packed reads -> H2D -> the same kernels -> D2H -> pinned rows, "
-                                     "same K steps, this rank; bound by the host link where the kernels outrun it (DESIGN.md 5)"},
-            "device_resident": {"reads_per_s": n_reads / ((plan_step_ms + kms[4]) * 1e-3), "ms_per_step": plan_step_ms + kms[4],
-                                "blocking_api_wall_ms_per_step": resident_wall * 1e3,
-                                "blocking_api_kernels_ms": {"plan": iso[5], "search": iso[0], "post": iso[1], "walk": iso[2], "score": iso[3], "total": iso[5] + iso[4]},
-                                "note": "plan + kernels of a batch whose packed reads are in HBM: HIP events of the timed steps (all kernels share one "
-                                        "stream, so the intervals are the kernels' own durations); the blocking_api figures are one slot alone through "
-                                        "cf_batch_plan + cf_classify, each call starting on an idle GPU"},
             "pcie_bytes_per_step": {"in": pcie_in, "out": pcie_out, "per_read": (pcie_in + pcie_out) / n_reads, "wire": a.wire if narrow or a.wire == "wide" else "wide",
                                     "note": "narrow: cf_dense_reads in (four bases per byte, one length for the batch, seeds, sparse N mask), CF_RESULTS_NARROW out (16-byte rows, one "
                                             "byte + 2ndBestScore per query); wide: cf_packed_reads in (32-base words, lengths, seeds), cf_row (24 bytes) + three words per query out — the same "
@@ -1055,7 +1104,7 @@ def main():
                          "whole_path_GBps": whole_bytes / ((plan_step_ms + kms[4]) * 1e-3) / 1e9,
                          "whole_path_frac": whole_bytes / ((plan_step_ms + kms[4]) * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                          "load_requests_per_launch": search_requests, "achieved_Grequests_per_s": search_requests / (kms[0] * 1e-3) / 1e9,
-                         "measured_random_Grequests_per_s": rand_gbps / 128.0,
+                         "measured_random_Grequests_per_s": rand_gbps / 128.0 if rand_gbps else None,
                          "frac_of_measured_request_rate": search_requests / (kms[0] * 1e-3) / 1e9 / (rand_gbps / 128.0) if rand_gbps else None,
                          "measured_random_128B_read_GBps": rand_gbps,
                          "frac_of_measured_random": achieved / rand_gbps if rand_gbps else None,
@@ -1074,10 +1123,24 @@ def main():
             "ops_per_read": {"ftab": ops.n_ftab / n_reads, "pair": ops.n_pair / n_reads, "pair2": ops.n_pair2 / n_reads,
                              "single": ops.n_single / n_reads, "ftab_wide": ops.n_ftab_wide / n_reads, "verify": ops.n_verify / n_reads, "pos_hits": ops.n_pos_hits / n_reads, "text_loads": ops.n_text_loads / n_reads,
                              "walk": ops.n_walk / n_reads, "rows": rows_out / n_reads,
-                             "printed_rows": len(res0[0]) / n_reads},
-            "general_kernel_queries": {"post": int(res0[5]["slow_post"]) / max(1, nq_all), "score": int(res0[5]["slow_score"]) / max(1, nq_all),
+                             "printed_rows": printed0 / n_reads},
+            "general_kernel_queries": {"post": int(info0["slow_post"]) / max(1, nq_all), "score": int(info0["slow_score"]) / max(1, nq_all),
                                        "note": "share of the queries the common-case post / score kernels (registers only) left to the general ones"},
         }
+        if a.full:                             # the legs that take runs of their own (host-to-host K steps, one slot alone)
+            res["config"]["host_to_host_reads_per_s"] = n_reads * world * a.steps / h2h_dt
+            res["config"]["host_to_host_ms_per_step"] = h2h_dt / max(1, a.steps) * 1e3
+            res.update({
+                "host_to_host": {"reads_per_s": n_reads * world * a.steps / h2h_dt, "ms_per_step": h2h_dt / max(1, a.steps) * 1e3,
+                                 "note": "the PCIe-inclusive rate (SURVEY 8d's scope, rounds 1-3's `value`): pinned packed reads -> H2D -> the same kernels -> D2H -> pinned rows, "
+                                         "same K steps, this rank; bound by the host link where the kernels outrun it (DESIGN.md 5)"},
+                "device_resident": {"reads_per_s": n_reads / ((plan_step_ms + kms[4]) * 1e-3), "ms_per_step": plan_step_ms + kms[4],
+                                    "blocking_api_wall_ms_per_step": resident_wall * 1e3,
+                                    "blocking_api_kernels_ms": {"plan": iso[5], "search": iso[0], "post": iso[1], "walk": iso[2], "score": iso[3], "total": iso[5] + iso[4]},
+                                    "note": "plan + kernels of a batch whose packed reads are in HBM: HIP events of the timed steps (all kernels share one "
+                                            "stream, so the intervals are the kernels' own durations); the blocking_api figures are one slot alone through "
+                                            "cf_batch_plan + cf_classify, each call starting on an idle GPU"},
+            })
         if merged_rows is not None:
             res["merged_report_rows"] = merged_rows
         # HBM traffic of the dominant kernel: rocprofv3 PMC passes cannot run inside this process, so the figure comes from the
@@ -1112,7 +1175,7 @@ def main():
                     res["roofline"]["traffic_source"] = "null: profiles/pmc_traffic.json was collected on other kernel sources (stale)"
         except Exception:
             pass
-        if not a.no_cpu and ns:
+        if a.full and not a.no_cpu and ns:
             try:
                 procs = max(1, nproc // a.cpu_threads)       # usable cores (cgroup quota) / threads per process
                 qps, tsv, n0, det = cpu_baseline(base, workdir, sample_codes, names, procs, a.cpu_threads, 5, paired)
@@ -1137,7 +1200,7 @@ def main():
     if rank == 0:
         # (only beside the headline itself: not when the sizes were overridden, nor in the one-rank process-group test mode)
         headline = not (a.genomes or a.genome_len or a.reads or a.read_len or a.hbm_budget_gb or os.environ.get("CF_BENCH_FORCE_DIST"))
-        if world == 1 and a.config == "2" and a.other_configs.strip() and headline:
+        if a.full and world == 1 and a.config == "2" and a.other_configs.strip() and headline:
             # the other workloads of BASELINE.json, each in a process of its own (its index needs the HBM this one holds)
             del slots, sets, last, res0
             clf.close(); ix.close()
@@ -1149,6 +1212,8 @@ def main():
                 except Exception as e:
                     res["cli_end_to_end"] = {"failed": repr(e)}
             res["other_configs"] = run_other_configs([c for c in a.other_configs.split(",") if c.strip()], a.other_steps, a.other_budget_s)
+        if a.dump_outputs and a.steps > 0:
+            write_outputs(a.dump_outputs, dumped)
         print(json.dumps(res))
     if dist is not None:
         dist.barrier()

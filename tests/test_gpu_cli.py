@@ -84,7 +84,7 @@ def test_bench_distributed_path_with_one_rank():
     import sys
     env = dict(os.environ, CF_BENCH_FORCE_DIST="1", CF_BENCH_DIR=tempfile.mkdtemp())
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(29600 + os.getpid() % 300), os.path.join(common.ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+           "--master-port", str(29600 + os.getpid() % 300), os.path.join(common.ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "2",
            "--warmup", "1", "--genomes", "32", "--genome-len", "200000", "--reads", "200000", "--cpu-sample", "20000"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -351,8 +351,9 @@ def _n_devices():
 
 def _need_two():
     # (asked inside the tests, not at import: the library's HIP runtime must not come up before torch's in the collecting process)
-    if _n_devices() < 2:
-        pytest.skip("needs two or more GPUs")
+    n = _n_devices()
+    if n < 2:
+        pytest.skip("needs 2 GPUs, found %d" % n)
 
 
 def test_counts_allreduce_group_over_real_devices():
@@ -422,7 +423,7 @@ def test_bench_under_torchrun_with_two_ranks():
     import sys
     env = dict(os.environ, CF_BENCH_DIR=tempfile.mkdtemp())
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(29900 + os.getpid() % 90), os.path.join(common.ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
+           "--master-port", str(29900 + os.getpid() % 90), os.path.join(common.ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3",
            "--warmup", "1", "--genomes", "32", "--genome-len", "200000", "--reads", "200000", "--cpu-sample", "20000", "--other-configs", ""]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -23,10 +23,10 @@ def run(args, d, env=None, exe=CLI, tag="o"):
     try:
         _, err = p.communicate(timeout=180)
     except subprocess.TimeoutExpired:
-        # a run that hangs: where its threads are (rocgdb is in the image), then an end to it
-        bt = subprocess.run(["/opt/rocm/bin/rocgdb", "-p", str(p.pid), "-batch", "-ex", "thread apply all bt 14"], capture_output=True, text=True, timeout=120)
+        # a run that hangs: an end to it, and what it wrote to stderr so far
         p.kill()
-        raise AssertionError("the run hangs: %s\n%s" % (" ".join([exe] + args), bt.stdout[-12000:]))
+        _, err = p.communicate()
+        raise AssertionError("the run hangs: %s\n%s" % (" ".join([exe] + args), (err or "")[-12000:]))
     assert p.returncode == 0, err
     return open(out, "rb").read(), open(rep, "rb").read(), err
 

@@ -13,6 +13,7 @@ import pytest
 
 import common
 from emu import emu as E
+from oracle import oracle as O
 
 BIN = os.path.join(common.ROOT, "centrifuge_amd", "bin")
 INSPECT = os.path.join(BIN, "centrifuge-inspect")
@@ -139,18 +140,17 @@ def test_build_then_inspect_round_trip(shift):
         assert a == b, common.first_diff(a.decode(), b.decode())
 
 
-# ------------------------------------------------ live against the reference's Perl scripts (build container only)
-REF_SCRIPTS = "/root/reference"
+# ------------------------------------------------ live against the reference's Perl scripts (oracle/_ref: `make -C oracle ref`)
+REF_SCRIPTS = O.REF_DIR
 
 
 @pytest.mark.skipif(not (os.path.exists(os.path.join(REF_SCRIPTS, "centrifuge-kreport")) and os.path.exists("/usr/bin/perl")),
-                    reason="the reference's Perl scripts are only in the build container")
+                    reason="the reference's Perl scripts are not in oracle/_ref (built by `make -C oracle ref`) or perl is missing")
 def test_kreport_and_promote_on_awkward_classification_files():
     """taxIDs that are not in the tree, unclassified rows, reads with three and more rows, reordered / extra columns:
     the same bytes as the Perl scripts (run from a scratch copy beside a shim `centrifuge-inspect`)."""
     import shutil
     import stat
-    from oracle import oracle as O
     if not O.have_ref():
         pytest.skip("oracle/_ref not built")
     idx = index_of("synth_small")

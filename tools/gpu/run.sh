@@ -46,13 +46,13 @@ for step in "$@"; do
     smoke)
       timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -2 $O/smoke.log ;;
     bench)
-      ( time timeout 1000 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/bench_wall.txt
+      ( time timeout 1000 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench_wall.txt
       grep real $O/bench_wall.txt; line $O/bench.json ;;
     bench2)
       timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu --other-configs "" > $O/bench2.json 2> $O/bench2.err; line $O/bench2.json ;;
     cli)           # the end-to-end leg alone (centrifuge-class on a FASTA file of config 2's reads): cli[:<reads>]
       n=50000000; [ "$arg" != "$name" ] && n=$arg
-      timeout 900 python bench.py --steps 3 --warmup 1 --no-cpu --other-configs , --cli-reads $n > $O/bench_cli.json 2> $O/bench_cli.err
+      timeout 900 python bench.py --full --steps 3 --warmup 1 --no-cpu --other-configs , --cli-reads $n > $O/bench_cli.json 2> $O/bench_cli.err
       python - $O/bench_cli.json <<'P'
 import json, sys
 j = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -63,7 +63,7 @@ P
     clitrace)      # the end-to-end leg with a kernel trace of centrifuge-class itself (every table): clitrace[:<reads>]
       n=20000000; [ "$arg" != "$name" ] && n=$arg
       mkdir -p $O/trace
-      CF_BENCH_CLI_TRACE=$O/trace timeout 900 python bench.py --steps 3 --warmup 1 --no-cpu --other-configs , --cli-reads $n > $O/bench_clitrace.json 2> $O/bench_clitrace.err
+      CF_BENCH_CLI_TRACE=$O/trace timeout 900 python bench.py --full --steps 3 --warmup 1 --no-cpu --other-configs , --cli-reads $n > $O/bench_clitrace.json 2> $O/bench_clitrace.err
       python tools/prof_summary.py $O > $O/summary_cli.txt 2>&1
       head -40 $O/summary_cli.txt ;;
     benchargs)     # bench2 with extra arguments (commas for blanks): benchargs:--wire,wide
@@ -74,7 +74,7 @@ P
       ( IFS=,; for kv in $arg; do export "$kv"; done
         timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu --other-configs "" > $f.json 2> $f.err ); echo "env $arg:"; line $f.json ;;
     cfg)
-      timeout 900 python bench.py --config $arg --other-configs "" --steps 20 --warmup 6 --cpu-sample 200000 > $O/bench_cfg$arg.json 2> $O/bench_cfg$arg.err
+      timeout 900 python bench.py --full --config $arg --other-configs "" --steps 20 --warmup 6 --cpu-sample 200000 > $O/bench_cfg$arg.json 2> $O/bench_cfg$arg.err
       line $O/bench_cfg$arg.json ;;
     cfgq)          # a preset alone, no CPU leg (quick A/B runs)
       timeout 600 python bench.py --config $arg --other-configs "" --steps 20 --warmup 6 --no-cpu > $O/bench_cfgq$arg.json 2> $O/bench_cfgq$arg.err
@@ -119,7 +119,7 @@ P
     curve)         # budget -> throughput curve of a preset: curve:<preset>:<gb,gb,...>
       preset=${arg%%:*}; gbs=${arg#*:}
       ( IFS=,; for gb in $gbs; do
-          timeout 400 python bench.py --config $preset --hbm-budget-gb $gb --steps 10 --warmup 6 --no-cpu --other-configs "" > $O/curve_${preset}_$gb.json 2> $O/curve_${preset}_$gb.err
+          timeout 400 python bench.py --full --config $preset --hbm-budget-gb $gb --steps 10 --warmup 6 --no-cpu --other-configs "" > $O/curve_${preset}_$gb.json 2> $O/curve_${preset}_$gb.err
           python - $O/curve_${preset}_$gb.json $gb <<'P'
 import json, sys
 try:

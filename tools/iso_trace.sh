@@ -8,7 +8,7 @@ TAG=${1:-iso}; shift || true
 R=$PWD; OUT=$R/gpurun_out/iso_$TAG; mkdir -p $OUT
 export TMPDIR=/tmp CF_BENCH_DIR=${CF_BENCH_DIR:-/tmp/cfb}
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python $R/bench.py --no-cpu --steps 3 --warmup 1 "$@" > $OUT/bench.json 2> $OUT/err.txt
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python $R/bench.py --full --no-cpu --steps 3 --warmup 1 "$@" > $OUT/bench.json 2> $OUT/err.txt
 cd $R
 python - "$OUT" <<'PY'
 import csv, glob, sys
