@@ -217,6 +217,7 @@ def lib():
         "cf_batch_upload": (i32, [vp, vp, vp, vp, u64, i32, vp]),
         "cf_batch_upload_text": (i32, [vp, C.POINTER(TextReads), vp, C.POINTER(TextInfo)]),
         "cf_batch_wait_text": (i32, [vp, C.POINTER(ResultsText)]),
+        "cf_text_column_of": (C.c_int32, [cp]), "cf_batch_set_text_columns": (i32, [vp, vp, u32]),
         "cf_counts_get_single": (i32, [vp, vp]),
         "cf_report_add_tuples": (i32, [vp, vp, u64]), "cf_report_adopt_device_tally": (i32, [vp, vp, vp, vp, u64]),
         "cf_batch_set_limits": (i32, [vp, u64, u64]),
@@ -236,6 +237,17 @@ def lib():
 
 class CfError(RuntimeError):
     pass
+
+
+# the columns of a formatted row (CF_COL_* of include/centrifuge_amd.h; Slot.set_text_columns)
+(COL_READ_ID, COL_SEQ_ID, COL_TAX_ID, COL_TAX_RANK, COL_TAX_NAME, COL_SCORE, COL_SCORE2, COL_HIT_LEN, COL_QUERY_LEN, COL_NUM_MATCHES,
+ COL_SEQ, COL_QUAL, COL_SEQ1, COL_QUAL1, COL_SEQ2, COL_QUAL2, COL_PLACEHOLDER, COL_ZERO) = range(18)
+TEXT_MAX_COLS = 32
+
+
+def text_column_of(name):
+    """a column's name as the reference spells it (SAM field names included) -> its code, or -1"""
+    return int(lib().cf_text_column_of(name.encode() if isinstance(name, str) else name))
 
 
 def _check(st):
@@ -600,8 +612,22 @@ class Slot:
             _check(self.L.cf_classify_async(self.clf.h, self.h, stream))
         return info
 
+    def set_text_columns(self, cols):
+        """the columns later wait_text() calls print: names (as --tab-fmt-cols spells them) or COL_* codes; [] = the default eight"""
+        codes = []
+        for c in cols:
+            if isinstance(c, (str, bytes)):
+                code = text_column_of(c)
+                if code < 0:
+                    raise CfError("unknown column name %r" % (c,))
+                codes.append(code)
+            else:
+                codes.append(int(c))
+        a = np.asarray(codes, dtype=np.int32)
+        _check(self.L.cf_batch_set_text_columns(self.h, a.ctypes.data if len(a) else None, len(a)))
+
     def wait_text(self):
-        """-> the batch's rows as the default columns' text (bytes), the perfect multi-assignment tuples (u32: n, n taxon indices, ...), info"""
+        """-> the batch's rows as text (bytes; the default columns, or those of set_text_columns), the perfect multi-assignment tuples (u32: n, n taxon indices, ...), info"""
         r = ResultsText()
         _check(self.L.cf_batch_wait_text(self.h, C.byref(r)))
         text = C.string_at(r.text, r.n_bytes) if r.n_bytes else b""

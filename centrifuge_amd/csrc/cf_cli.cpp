@@ -41,6 +41,8 @@ namespace {
 
 enum Col { C_READ_ID, C_SEQ_ID, C_TAX_ID, C_TAX_RANK, C_TAX_NAME, C_SCORE, C_SCORE2, C_HIT_LEN, C_QUERY_LEN, C_NUM_MATCHES,
            C_SEQ, C_QUAL, C_SEQ1, C_QUAL1, C_SEQ2, C_QUAL2, C_PLACEHOLDER, C_ZERO };
+static_assert(C_READ_ID == CF_COL_READ_ID && C_TAX_NAME == CF_COL_TAX_NAME && C_NUM_MATCHES == CF_COL_NUM_MATCHES && C_SEQ == CF_COL_SEQ &&
+              C_QUAL2 == CF_COL_QUAL2 && C_PLACEHOLDER == CF_COL_PLACEHOLDER && C_ZERO == CF_COL_ZERO, "the kinds above are the library's column codes");
 
 struct Opts {
     std::string index, outFile, reportFile = "centrifuge_report.tsv";
@@ -89,7 +91,8 @@ void usage(std::FILE *f) {
         " GPUs:    --gpus <N|all> (index replicated on N devices from --device <int> on, batches dealt to them, per-taxon counters\n"
         "          all-reduced with RCCL, output in input order)  --gpu-list <d,..>  --slots <int> (batches in flight per device, 2)\n"
         "          --host-io (reads are parsed and rows printed by host threads for every input; default: plain FASTA / FASTQ files go up as\n"
-        "          text and the default columns come back as text, formatted on the device — same bytes either way)\n"
+        "          text and the rows come back as text, formatted on the device — the default columns, any --tab-fmt-cols list of up\n"
+        "          to 32 columns, --out-fmt sam — same bytes either way)\n"
         " Index:   --hbm-budget-gb <float> (device memory the index may take, files + derived tables; default: what is free less a\n"
         "          reserve for the batch slots)  --small-range-rows <-1|0|2..15> (search ranges of up to that many rows are finished\n"
         "          against the text; 0 = decided from how repeat-rich the indexed collection is, -1 = off; results do not depend on it)\n"
@@ -110,18 +113,10 @@ std::vector<std::string> splitComma(const std::string &s) {
     return out;
 }
 
-int colOf(const std::string &n) {
-    static const std::pair<const char *, int> kMap[] = {
-        {"readID", C_READ_ID}, {"seqID", C_SEQ_ID}, {"taxLevel", C_TAX_RANK}, {"taxRank", C_TAX_RANK}, {"taxID", C_TAX_ID},
-        {"taxName", C_TAX_NAME}, {"score", C_SCORE}, {"2ndBestScore", C_SCORE2}, {"hitLength", C_HIT_LEN},
-        {"queryLength", C_QUERY_LEN}, {"numMatches", C_NUM_MATCHES}, {"readSeq", C_SEQ}, {"readQual", C_QUAL},
-        {"readSeq1", C_SEQ1}, {"readQual1", C_QUAL1}, {"readSeq2", C_SEQ2}, {"readQual2", C_QUAL2},
-        {"SEQ1", C_SEQ1}, {"QUAL1", C_QUAL1}, {"SEQ2", C_SEQ2}, {"QUAL2", C_QUAL2},
-        // SAM-style names (centrifuge.cpp:497-508)
-        {"QNAME", C_READ_ID}, {"FLAG", C_ZERO}, {"RNAME", C_TAX_ID}, {"POS", C_ZERO}, {"MAPQ", C_ZERO}, {"CIGAR", C_PLACEHOLDER},
-        {"RNEXT", C_SEQ_ID}, {"PNEXT", C_ZERO}, {"TLEN", C_QUERY_LEN}, {"SEQ", C_SEQ}, {"QUAL", C_QUAL}};
-    for (const auto &kv : kMap) if (n == kv.first) return kv.second;
-    die("Column definition " + n + " invalid.");
+int colOf(const std::string &n) {                        // (the table of names is the library's: cf_text_column_of)
+    const int32_t c = cf_text_column_of(n.c_str());
+    if (c < 0) die("Column definition " + n + " invalid.");
+    return (int)c;
 }
 
 int rankSlot(const std::string &r) {
@@ -780,7 +775,21 @@ struct Runner {
             if (g.rep) CF_TRY(cf_report_add_narrow(g.rep, b.rows16.data(), b.qinfo.data(), b.r.pk.lens.p, 0, mates ? 1 : 0, b.nq));
             lap(g.tm.report);
             OutBuf &ob = *hostOut[gi];
-            if (b.nq) formatDefault(b, b.rows16, b.nRows, b.score2, 0, b.nq, ob); else ob.len = 0;
+            if (!b.nq) ob.len = 0;
+            else if (defaultCols) formatDefault(b, b.rows16, b.nRows, b.score2, 0, b.nq, ob);
+            else {
+                // any other columns: the general formatter, which reads wide rows (the block's own: a few thousand reads)
+                cf_results_narrow nr{};
+                nr.rows = b.rows16.data(); nr.qinfo = b.qinfo.data(); nr.score2 = b.score2.data(); nr.n_queries = b.nq; nr.total_rows = res.total_rows;
+                if (b.rows.size() < res.total_rows) b.rows.resize(res.total_rows);
+                if (b.maxScore.size() < b.nq) b.maxScore.resize(b.nq);
+                CF_TRY(cf_results_narrow_expand(g.dev->ix, &nr, b.r.pk.lens.p, 0, mates ? 1 : 0, b.rows.data(), b.nRows.data(), b.maxScore.data()));
+                std::string s;
+                s.reserve(b.nq * 64);
+                formatRange(b, b.rows, b.nRows, b.score2, 0, b.nq, s);
+                std::memcpy(ob.room(s.size()), s.data(), s.size());
+                ob.len = s.size();
+            }
             text = ob.p.get(); nText = ob.len;
             lap(g.tm.format);
         }
@@ -1038,10 +1047,10 @@ int run(int argc, const char **argv) {
         p.host_taxids = o.hostTaxids.data(); p.n_host = (int32_t)o.hostTaxids.size();
         p.exclude_taxids = o.excludeTaxids.data(); p.n_exclude = (int32_t)o.excludeTaxids.size();
         for (auto &d : R.devs) CF_TRY(cf_classifier_create(d.ix, &p, &d.clf));
-        // The device text path (round 6): whole blocks of a plain FASTA / FASTQ file up as text, the default columns back as text —
-        // without trimming or a skip, the default columns, -k <= 63 (the narrow rows' six bits).  Every GPU thread
+        // The device text path (round 6): whole blocks of a plain FASTA / FASTQ file up as text, the rows back as text — without
+        // trimming or a skip, up to CF_TEXT_MAX_COLS columns (cf_batch_set_text_columns), -k <= 63 (the narrow rows' six bits).  Every GPU thread
         // then also reads its blocks and writes its text, so there are more of them (each with a slot on the device).
-        R.textCapable = !ordered && R.defaultCols && (o.format == ReadFormat::Fasta || o.format == ReadFormat::Fastq) &&
+        R.textCapable = !ordered && o.cols.size() <= CF_TEXT_MAX_COLS && (o.format == ReadFormat::Fasta || o.format == ReadFormat::Fastq) &&
                         o.trim5 == 0 && o.trim3 == 0 && o.skip == 0 && o.khits <= 63 && !o.hostIo &&
                         !(cfamd::cf_knob("CF_CLI_DEVICE_TEXT") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_TEXT")));
         const int slots = ordered ? 1 : (R.textCapable && !o.slotsSet) ? std::max(2, std::min(6, o.threads / 2)) : o.slots;
@@ -1051,6 +1060,10 @@ int run(int argc, const char **argv) {
             g.dev = &R.devs[t / (size_t)slots];
             CF_TRY(cf_stream_create(g.dev->id, &g.stream));
             CF_TRY(cf_batch_alloc(g.dev->clf, 0, 0, &g.slot));
+            if (R.textCapable && !R.defaultCols) {               // (the default columns: the slot's default program)
+                const std::vector<int32_t> prog(o.cols.begin(), o.cols.end());
+                CF_TRY(cf_batch_set_text_columns(g.slot, prog.data(), (uint32_t)prog.size()));
+            }
             if (!ordered) CF_TRY(cf_report_create(R.ix, &g.rep));
         }
         if (R.textCapable) { for (size_t t = 0; t < R.gts.size(); t++) R.hostOut.push_back(new Runner::OutBuf()); }

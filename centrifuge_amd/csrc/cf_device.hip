@@ -279,6 +279,8 @@ __global__ void __launch_bounds__(256) k_text_records(DTextRec d) { text_record_
 __global__ void __launch_bounds__(256) k_text_pack(DTextPack d) { text_pack_body(d, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_size(DTextFmt f) { fmt_size_body(f, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_write(DTextFmt f) { fmt_write_body(f, cf_global_thread()); }
+__global__ void __launch_bounds__(256) k_fmt_cols_size(DTextFmt f, TextCols pc) { fmt_cols_size_body(f, pc, cf_global_thread()); }
+__global__ void __launch_bounds__(256) k_fmt_cols_write(DTextFmt f, TextCols pc) { fmt_cols_write_body(f, pc, cf_global_thread()); }
 template <int G, bool WRITE>
 __global__ void __launch_bounds__(256) k_restore(DIndex ix, DRestore r) { restore_body<G, WRITE>(ix, r); }
 __global__ void __launch_bounds__(256) k_restore_rank(const uint64_t *sumIn, const uint32_t *nextIn, uint64_t *sumOut, uint32_t *nextOut, uint32_t nElem) {
@@ -390,6 +392,10 @@ struct cf_classifier {
     DevBuf<uint32_t> fmtUidOff, fmtRankOff, fmtTaxOff;
     uint32_t fmtIdxZero = 0;
     bool fmtMade = false;
+    // ... and the two a taxRank / taxName column repeats (cf_batch_set_text_columns), made when a program first names one of them
+    DevBuf<uint8_t> fmtTaxStrs;
+    DevBuf<uint32_t> fmtTrankOff, fmtTnameOff;
+    bool fmtTaxMade = false;
     std::mutex fmtMu;
 };
 
@@ -445,7 +451,9 @@ struct cf_batch {
     // the text forms: the uploaded block (it stays: the readIDs are copied out of it), what the record pass leaves per read, the
     // formatted rows
     DevBuf<uint8_t> text, textOut;
-    DevBuf<uint32_t> txCnt, txPos, txSeqOff, txIdOff, txIdLen, txSize, txTuples, txTileC;
+    DevBuf<uint32_t> txCnt, txPos, txSeqOff, txIdOff, txIdLen, txQualOff, txSize, txTuples, txTileC;
+    TextCols textCols{};                     // cf_batch_set_text_columns: the columns cf_batch_wait_text prints (nCols 0: the default eight, by the default kernels)
+    bool textFastq = false;                  // the block that is loaded is FASTQ (txQualOff holds its quality lines' places)
     DevBuf<uint64_t> txBase, txOutOff, txTileA;
     DevBuf<TextStatus> txSt;
     PinBuf<TextStatus> hTxSt;
@@ -1978,6 +1986,7 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
     bt->txTileA.ensure(scan_tiles_for(std::max(pieces[0], pieces[nBlocks - 1])) + 1); bt->txTileC.ensure(scan_tiles_for(std::max(pieces[0], pieces[nBlocks - 1])) + 1);
     bt->rlen.ensure(readCap + 16); bt->seeds.ensure(readCap + 16);
     bt->txSeqOff.ensure(readCap + 16); bt->txIdOff.ensure(readCap + 16); bt->txIdLen.ensure(readCap + 16);
+    if (!fasta) bt->txQualOff.ensure(readCap + 16);
     bt->txSt.ensure(1); bt->hTxSt.ensure(1); bt->hTxTotal.ensure(2);
     *info = cf_text_info{};
     bt->loaded = false; bt->planned = false; bt->running = false; bt->finished = false;
@@ -1996,7 +2005,8 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
         scan_enqueue<SCAN_PLAIN>(cnt, pieces[k], base, nullptr, bt->txTileA.p, bt->txTileC.p, st);
         if (pieces[k]) hipLaunchKernelGGL(k_text_mark, gp, bl, 0, st, m);
         DTextRec d{text, nBs[k], pos, base + pieces[k], posCap[k], (uint32_t)recCap[k], (uint32_t)in->format, seed0,
-                   bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], (uint32_t)nBlocks, (uint32_t)k};
+                   bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], (uint32_t)nBlocks, (uint32_t)k,
+                   fasta ? nullptr : bt->txQualOff.p};
         hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
         HIP_OK(hipMemcpyAsync(bt->hTxTotal.p + k, base + pieces[k], 8, hipMemcpyDeviceToHost, st));
     }
@@ -2015,6 +2025,7 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
     bindBatch(bt);
     HIP_OK(hipEventRecord(bt->ev[8], st));
     bt->fromText = true; bt->fromBytes = false; bt->densePending = 0; bt->revMade = false; bt->nmaskZeroOf = nullptr;   // (k_text_pack writes every mask word)
+    bt->textFastq = !fasta;
     bt->loaded = true;
     info->n_reads = nReads; info->n_bases = ts.bases(); info->max_len = ts.maxLen;
 }
@@ -2259,6 +2270,60 @@ static void makeFormatTables(cf_classifier *cl) {
     cl->fmtMade = true;
 }
 
+// ... and per taxon its rank's and its name's string (the taxRank / taxName columns), with tax ID 0's behind the last taxon's:
+// what an unclassified row prints
+static void makeTaxTextTables(cf_classifier *cl) {
+    std::lock_guard<std::mutex> lk(cl->fmtMu);
+    if (cl->fmtTaxMade) return;
+    const cf_index *ix = cl->ix;
+    const size_t nTaxa = ix->h.taxa.size();
+    std::vector<uint8_t> strs;
+    std::vector<uint32_t> rankOff(nTaxa + 2), nameOff(nTaxa + 2);
+    auto put = [&](const char *x) { if (x) strs.insert(strs.end(), x, x + std::strlen(x)); };
+    for (size_t i = 0; i <= nTaxa; i++) { rankOff[i] = (uint32_t)strs.size(); put(cf_tax_rank_string(cf_tax_rank(ix, i < nTaxa ? ix->h.taxa[i] : 0))); }
+    rankOff[nTaxa + 1] = (uint32_t)strs.size();
+    for (size_t i = 0; i <= nTaxa; i++) { nameOff[i] = (uint32_t)strs.size(); put(cf_tax_name(ix, i < nTaxa ? ix->h.taxa[i] : 0)); }
+    nameOff[nTaxa + 1] = (uint32_t)strs.size();
+    if (strs.size() >= 0xffffffffull) throw ArgError("the index's taxon names exceed 4 GB");
+    strs.resize(strs.size() + 16, 0);
+    cl->fmtTaxStrs.upload(strs); cl->fmtTrankOff.upload(rankOff); cl->fmtTnameOff.upload(nameOff);
+    cl->fmtTaxMade = true;
+}
+
+// the one table of column names: the reference's spellings (centrifuge.cpp:484-520), the SAM field names among them
+int32_t cf_text_column_of(const char *name) {
+    static const struct { const char *name; int32_t col; } kMap[] = {
+        {"readID", CF_COL_READ_ID}, {"seqID", CF_COL_SEQ_ID}, {"taxLevel", CF_COL_TAX_RANK}, {"taxRank", CF_COL_TAX_RANK}, {"taxID", CF_COL_TAX_ID},
+        {"taxName", CF_COL_TAX_NAME}, {"score", CF_COL_SCORE}, {"2ndBestScore", CF_COL_SCORE2}, {"hitLength", CF_COL_HIT_LEN},
+        {"queryLength", CF_COL_QUERY_LEN}, {"numMatches", CF_COL_NUM_MATCHES}, {"readSeq", CF_COL_SEQ}, {"readQual", CF_COL_QUAL},
+        {"readSeq1", CF_COL_SEQ1}, {"readQual1", CF_COL_QUAL1}, {"readSeq2", CF_COL_SEQ2}, {"readQual2", CF_COL_QUAL2},
+        {"SEQ1", CF_COL_SEQ1}, {"QUAL1", CF_COL_QUAL1}, {"SEQ2", CF_COL_SEQ2}, {"QUAL2", CF_COL_QUAL2},
+        // SAM-style names (centrifuge.cpp:497-508)
+        {"QNAME", CF_COL_READ_ID}, {"FLAG", CF_COL_ZERO}, {"RNAME", CF_COL_TAX_ID}, {"POS", CF_COL_ZERO}, {"MAPQ", CF_COL_ZERO}, {"CIGAR", CF_COL_PLACEHOLDER},
+        {"RNEXT", CF_COL_SEQ_ID}, {"PNEXT", CF_COL_ZERO}, {"TLEN", CF_COL_QUERY_LEN}, {"SEQ", CF_COL_SEQ}, {"QUAL", CF_COL_QUAL}};
+    if (!name) return -1;
+    for (const auto &kv : kMap) if (!std::strcmp(name, kv.name)) return kv.col;
+    return -1;
+}
+
+cf_status cf_batch_set_text_columns(cf_batch *bt, const int32_t *cols, uint32_t nCols) {
+    static_assert(CF_TEXT_MAX_COLS == kTextMaxCols && CF_COL_ZERO == kColZero && CF_COL_READ_ID == kColReadId && CF_COL_SEQ == kColSeq &&
+                  CF_COL_QUAL2 == kColQual2 && CF_COL_TAX_NAME == kColTaxName && CF_COL_NUM_MATCHES == kColNumMatches, "the public column codes are the kernels'");
+    if (!bt || (nCols && !cols)) return CF_ERR_ARG;
+    if (nCols > CF_TEXT_MAX_COLS) { g_err = "cf_batch_set_text_columns: " + std::to_string(nCols) + " columns (at most CF_TEXT_MAX_COLS = 32)"; return CF_ERR_ARG; }
+    TextCols pc{};
+    for (uint32_t i = 0; i < nCols; i++) {
+        if (cols[i] < 0 || cols[i] >= (int32_t)kColCount) { g_err = "cf_batch_set_text_columns: unknown column code " + std::to_string(cols[i]); return CF_ERR_ARG; }
+        pc.col[i] = (uint8_t)cols[i];
+    }
+    pc.nCols = nCols;
+    // the default eight, spelled out, are the default program: the default kernels print them
+    static const uint8_t kDefault[8] = {kColReadId, kColSeqId, kColTaxId, kColScore, kColScore2, kColHitLen, kColQueryLen, kColNumMatches};
+    if (nCols == 8 && !std::memcmp(pc.col, kDefault, 8)) pc = TextCols{};
+    bt->textCols = pc;
+    return CF_OK;
+}
+
 // The results of a batch that came as text, as text: the default columns formatted on the device from the rows the kernels left
 // there (none of them crosses the link), and the perfect multi-assignment tuples the report's EM needs beside the device's counters.
 cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) {
@@ -2279,6 +2344,10 @@ cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) {
             return;
         }
         makeFormatTables(cl);
+        const TextCols pc = bt->textCols;
+        bool needTax = false;
+        for (uint32_t i = 0; i < pc.nCols; i++) needTax = needTax || pc.col[i] == kColTaxRank || pc.col[i] == kColTaxName;
+        if (needTax) makeTaxTextTables(cl);
         hipStream_t st = bt->stream;
         const uint64_t nq = bt->nQueries;
         const uint32_t nTaxa = (uint32_t)cl->ix->h.taxa.size();
@@ -2295,17 +2364,23 @@ cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) {
         f.nRefs = (uint32_t)cl->ix->h.uid.size(); f.nTaxa = nTaxa; f.idxZero = cl->fmtIdxZero;
         f.size = bt->txSize.p; f.outOff = bt->txOutOff.p; f.single = cl->counts.p + 2 * (size_t)nTaxa;
         f.tuples = bt->txTuples.p; f.tuplesCap = (uint32_t)tuplesCap; f.st = bt->txSt.p;
+        if (pc.nCols) {
+            if (needTax) { f.taxStrs = cl->fmtTaxStrs.p; f.trankOff = cl->fmtTrankOff.p; f.tnameOff = cl->fmtTnameOff.p; }
+            f.woff = bt->woff.p; f.bases = bt->bases.p; f.nmask = bt->nmask.p; f.qualOff = bt->textFastq ? bt->txQualOff.p : nullptr;
+        }
         const dim3 bl(256), gq((unsigned)std::max<uint64_t>(1, (nq + 255) / 256));
         uint64_t total = 0;
         if (nq) {
-            hipLaunchKernelGGL(k_fmt_size, gq, bl, 0, st, f);
+            if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_size, gq, bl, 0, st, f, pc);
+            else hipLaunchKernelGGL(k_fmt_size, gq, bl, 0, st, f);
             scan_enqueue<SCAN_PLAIN>(bt->txSize.p, nq, bt->txOutOff.p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
             HIP_OK(hipMemcpyAsync(bt->hTxTotal.p, bt->txOutOff.p + nq, 8, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
             total = *bt->hTxTotal.p;
             bt->textOut.ensure(total + 16); bt->hTextOut.ensure(total + 16);
             f.out = bt->textOut.p; f.outCap = total;
-            hipLaunchKernelGGL(k_fmt_write, gq, bl, 0, st, f);
+            if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_write, gq, bl, 0, st, f, pc);
+            else hipLaunchKernelGGL(k_fmt_write, gq, bl, 0, st, f);
             HIP_OK(hipMemcpyAsync(bt->hTextOut.p, bt->textOut.p, total, hipMemcpyDeviceToHost, st));
             HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));

@@ -10,7 +10,7 @@
 //          lines whose characters are A C G T N in either case, at least one of them
 //   FASTQ  four lines per record: '@' + non-empty name without '\r'; a non-empty line of A C G T N in either case; a line that
 //          starts with '+'; as many quality characters (all >= 33) as bases; the block ends with the last record's '\n'
-// Egress: the default eight columns of AlnSinkSam::appendMate (aln_sink.h:2279-2337; centrifuge.cpp:520) are formatted here from
+// Egress: the default eight columns of AlnSinkSam::appendMate — or any other list of its columns (fmt_cols_*_body, at the end) — (aln_sink.h:2279-2337; centrifuge.cpp:520) are formatted here from
 // the narrow rows the batch leaves on the device, the readID copied out of the uploaded block (aln_sink.h:2203-2217), into a
 // buffer the host only write()s; and the part of SpeciesMetrics (aln_sink.h:142-172) the per-taxon counters of count_body do not
 // hold — the perfect single assignments and the perfect multi-assignment tuples the EM runs on — is tallied by the same pass.
@@ -121,6 +121,7 @@ struct DTextRec {
     // mates: two blocks in one buffer (text = this block's first byte, textBase = its place in the buffer: the places left for the
     // later passes count from the buffer's start), record r of block `mate` is read stride * r + mate of the batch
     uint32_t textBase, stride, mate;
+    uint32_t *qualOff;           // FASTQ: first byte of the record's quality line (nullptr: not kept; the readQual columns of fmt_cols_write_body)
 };
 CF_DEV bool tx_isspace(uint32_t c) { return c == ' ' || (c >= 9 && c <= 13); }
 // base letter -> 0..3, 4 = N, 5 = not a plain base letter
@@ -250,6 +251,7 @@ CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
             d.idOff[w] = d.textBase + (uint32_t)(ls + 1); d.idLen[w] = idLen;
             d.seqOff[w] = d.textBase + (uint32_t)(n0 + 1);
             flags |= tx_bases(d.text, n0 + 1, n1, seed, len);
+            if (d.qualOff) d.qualOff[w] = d.textBase + (uint32_t)(n2 + 1);
             if (n2 <= n1 + 1 || d.text[n1 + 1] != '+') flags |= kTxBadPlus;
             if (n3 - n2 != n1 - n0) flags |= kTxQualLen;
             else {
@@ -352,6 +354,14 @@ struct DTextFmt {
     uint32_t *tuples;
     uint32_t tuplesCap;
     TextStatus *st;
+    // what the columns beyond the default eight need (fmt_cols_size_body / fmt_cols_write_body; the default bodies read none of it):
+    // per taxon its rank's and its name's string — nTaxa + 1 of each, the last one tax ID 0's, which an unclassified row prints —,
+    // the batch's packed reads (readSeq is printed from them: the uploaded text may be wrapped or lower case), and per read the
+    // place of its quality line in `text` (nullptr: FASTA, whose qualities are 'I' throughout)
+    const uint8_t *taxStrs;
+    const uint32_t *trankOff, *tnameOff;     // places in taxStrs
+    const uint64_t *woff, *bases;
+    const uint32_t *nmask, *qualOff;
 };
 CF_DEV uint32_t tx_digits(uint32_t v) {
     return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u : v < 10000000u ? 7u : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
@@ -459,6 +469,240 @@ CF_DEV void fmt_write_body(const DTextFmt &f, uint32_t q, uint8_t *lds = nullptr
     if (viaLds) {
         // every lane's rows are in LDS (the operations of a wavefront on its LDS retire in order; the fence keeps the compiler's
         // hands off the order): out they go, dword j of the stretch by lane j mod 64
+        cf_compiler_fence();
+        const uint32_t total = phase + (uint32_t)(segEnd - segBegin);
+        uint8_t *const dst = f.out + (segBegin - phase);                  // a dword boundary of the output
+        for (uint32_t j = lane; 4 * j < total; j += CF_WAVE) {
+            const uint32_t lo = 4 * j, hi = lo + 4;
+            if (lo >= phase && hi <= total) {
+                uint32_t v;
+                __builtin_memcpy(&v, lds + lo, 4);
+                *reinterpret_cast<uint32_t *>(dst + lo) = v;
+            } else
+                for (uint32_t k = lo < phase ? phase : lo; k < (hi < total ? hi : total); k++) dst[k] = lds[k];
+        }
+        cf_compiler_fence();
+    }
+    // one atomic per taxon and wavefront: the lanes that name the same taxon as the lowest waiting lane are counted by it
+    bool waiting = oneTaxon != 0xffffffffu;
+    for (;;) {
+        const uint64_t w = cf_ballot(waiting);
+        if (!w) break;
+        const uint32_t lead = cf_shfl(oneTaxon, cf_ctz64(w));
+        const uint64_t same = cf_ballot(waiting && oneTaxon == lead);
+        if (waiting && oneTaxon == lead) {
+            if ((uint32_t)cf_ctz64(same) == cf_lane()) cf_atomic_add(&f.single[lead], (unsigned long long)cf_popc64(same));
+            waiting = false;
+        }
+    }
+    if (live && q + 1 == f.nQueries) f.st->outBytes = f.outOff[f.nQueries];
+}
+
+// ---- egress: any list of columns (--tab-fmt-cols, --out-fmt sam: centrifuge.cpp:484-520; the fields of AlnSinkSam::appendMate,
+// aln_sink.h:2279-2337).  The program — up to kTextMaxCols column codes — comes by value.  The short fields (names, numbers) are
+// printed lane by lane as in the default bodies; the LONG ones (readSeq*, readQual*: a read's length each) are not: a 150-base row
+// would be 150 one-byte stores per lane, scattered over the wavefront's stretch.  They are written by the WHOLE wavefront, one
+// field after the other, in aligned dwords — the sequence expanded from the batch's 2-bit words in registers, 16 bases per lane.
+constexpr uint32_t kTextMaxCols = 32;
+enum : uint32_t {
+    kColReadId = 0, kColSeqId, kColTaxId, kColTaxRank, kColTaxName, kColScore, kColScore2, kColHitLen, kColQueryLen, kColNumMatches,
+    kColSeq, kColQual, kColSeq1, kColQual1, kColSeq2, kColQual2, kColPlaceholder, kColZero, kColCount
+};
+struct TextCols { uint8_t col[kTextMaxCols]; uint32_t nCols; };
+CF_DEV bool tx_col_long(uint32_t c) { return c >= kColSeq && c <= kColQual2; }
+CF_DEV bool tx_col_qual(uint32_t c) { return c == kColQual || c == kColQual1 || c == kColQual2; }
+// what a query's rows share
+struct FmtQuery { uint32_t ra, len1, len2, qlen, n, idn, s2; uint64_t f0; };
+CF_DEV FmtQuery fmt_query(const DTextFmt &f, uint32_t q) {
+    FmtQuery Q;
+    Q.ra = f.paired ? 2 * q : q;
+    Q.len1 = f.rlen[Q.ra]; Q.len2 = f.paired ? f.rlen[Q.ra + 1] : 0u;
+    Q.qlen = Q.len1 + Q.len2;
+    Q.n = f.qinfo[q] & 0x3fu; Q.idn = f.idLen[Q.ra]; Q.s2 = f.score2[q];
+    Q.f0 = Q.n ? f.rowFirst[q] : 0;
+    return Q;
+}
+CF_DEV uint32_t fmt_long_len(const DTextFmt &f, const FmtQuery &Q, uint32_t c) {
+    if (c == kColSeq || c == kColQual) return f.paired ? Q.len1 + 1 + Q.len2 : Q.len1;        // seq1_seq2
+    if (c == kColSeq1 || c == kColQual1) return Q.len1;
+    return f.paired ? Q.len2 : 0u;                                                                // (no second mate: empty)
+}
+// bytes of column c in a row of the query (uncl: the one row of a query without rows — seqID "unclassified", taxID, score, hitLength 0)
+CF_DEV uint32_t fmt_col_len(const DTextFmt &f, const FmtQuery &Q, uint32_t c, bool uncl, const TextRow &row) {
+    const uint32_t t = row.tidx < f.nTaxa ? row.tidx : 0u, tz = uncl ? f.nTaxa : t;
+    switch (c) {
+        case kColReadId: return Q.idn;
+        case kColSeqId:
+            if (uncl) return 12u;
+            return f.taxLeaf[t] && row.uniqueID < f.nRefs ? f.uidOff[row.uniqueID + 1] - f.uidOff[row.uniqueID] : f.rankOff[t + 1] - f.rankOff[t];
+        case kColTaxId: return uncl ? 1u : f.taxOff[t + 1] - f.taxOff[t];
+        case kColTaxRank: return f.trankOff[tz + 1] - f.trankOff[tz];
+        case kColTaxName: return f.tnameOff[tz + 1] - f.tnameOff[tz];
+        case kColScore: return uncl ? 1u : tx_digits(row.score);
+        case kColScore2: return tx_digits(Q.s2);
+        case kColHitLen: return uncl ? 1u : tx_digits(row.hitLen);
+        case kColQueryLen: return tx_digits(Q.qlen);
+        case kColNumMatches: return tx_digits(Q.n ? Q.n : 1u);
+        case kColPlaceholder: return 2u;
+        case kColZero: return 1u;
+        default: return fmt_long_len(f, Q, c);
+    }
+}
+// a short column printed at w
+CF_DEV uint8_t *fmt_col_put(const DTextFmt &f, const FmtQuery &Q, uint32_t c, bool uncl, const TextRow &row, uint8_t *w) {
+    const uint32_t t = row.tidx < f.nTaxa ? row.tidx : 0u, tz = uncl ? f.nTaxa : t;
+    switch (c) {
+        case kColReadId: return tx_copy(w, f.text + f.idOff[Q.ra], Q.idn);
+        case kColSeqId: {
+            if (uncl) { const uint8_t kU[] = {'u', 'n', 'c', 'l', 'a', 's', 's', 'i', 'f', 'i', 'e', 'd'}; for (uint32_t i = 0; i < sizeof kU; i++) *w++ = kU[i]; return w; }
+            if (f.taxLeaf[t] && row.uniqueID < f.nRefs) return tx_copy(w, f.strs + f.uidOff[row.uniqueID], f.uidOff[row.uniqueID + 1] - f.uidOff[row.uniqueID]);
+            return tx_copy(w, f.strs + f.rankOff[t], f.rankOff[t + 1] - f.rankOff[t]);
+        }
+        case kColTaxId: if (uncl) { *w++ = '0'; return w; } return tx_copy(w, f.strs + f.taxOff[t], f.taxOff[t + 1] - f.taxOff[t]);
+        case kColTaxRank: return tx_copy(w, f.taxStrs + f.trankOff[tz], f.trankOff[tz + 1] - f.trankOff[tz]);
+        case kColTaxName: return tx_copy(w, f.taxStrs + f.tnameOff[tz], f.tnameOff[tz + 1] - f.tnameOff[tz]);
+        case kColScore: return tx_put(w, uncl ? 0u : row.score);
+        case kColScore2: return tx_put(w, Q.s2);
+        case kColHitLen: return tx_put(w, uncl ? 0u : row.hitLen);
+        case kColQueryLen: return tx_put(w, Q.qlen);
+        case kColNumMatches: return tx_put(w, Q.n ? Q.n : 1u);
+        case kColPlaceholder: *w++ = '*'; *w++ = '0'; return w;      // (the reference's switch falls through "" -> "*" -> "0": aln_sink.h:2322-2324)
+        case kColZero: *w++ = '0'; return w;
+        default: return w + fmt_long_len(f, Q, c);                   // a long column: left to the wavefront
+    }
+}
+CF_DEV void fmt_cols_size_body(const DTextFmt &f, const TextCols &pc, uint32_t q) {
+    if (q >= f.nQueries) return;
+    const FmtQuery Q = fmt_query(f, q);
+    const bool uncl = Q.n == 0;
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < (uncl ? 1u : Q.n); i++) {
+        const TextRow row = uncl ? TextRow{0, 0, 0, 0} : f.rows[Q.f0 + i];
+        total += pc.nCols;                                               // the tabs between the columns and the '\n'
+        for (uint32_t k = 0; k < pc.nCols; k++) total += fmt_col_len(f, Q, pc.col[k], uncl, row);
+    }
+    f.size[q] = total;
+}
+// ---- the long fields: every lane of the wavefront calls these with the same arguments (lane: its number).  The field goes to dst, whose
+// place in the output is `at` bytes past a dword boundary (dst itself may point into the LDS stage, which keeps that phase): the
+// ragged ends byte by byte, the dwords between them whole.
+// n bytes from text[src..) — or, text == nullptr, that many 'I'
+CF_DEV void fmt_wave_bytes(uint8_t *dst, uint32_t at, const uint8_t *text, uint64_t src, uint32_t n, uint32_t lane) {
+    uint32_t head = (4u - (at & 3u)) & 3u;
+    if (head > n) head = n;
+    const uint32_t mid = (n - head) >> 2, tail = (n - head) & 3u;
+    for (uint32_t i = lane; i < head; i += CF_WAVE) dst[i] = text ? text[src + i] : (uint8_t)'I';
+    for (uint32_t j = lane; j < mid; j += CF_WAVE) {
+        const uint32_t v = text ? (uint32_t)tx_load8(text, src + head + 4 * j) : 0x49494949u;
+        __builtin_memcpy(__builtin_assume_aligned(dst + head + 4 * j, 4), &v, 4);
+    }
+    for (uint32_t i = head + 4 * mid + lane; i < head + 4 * mid + tail; i += CF_WAVE) dst[i] = text ? text[src + i] : (uint8_t)'I';
+}
+CF_DEV uint32_t tx_letter(uint32_t code, uint32_t isN) { return isN ? (uint32_t)'N' : (0x54474341u >> (8u * code)) & 0xffu; }   // "ACGT"
+CF_DEV uint32_t tx_base_at(const uint64_t *w, const uint32_t *m, uint32_t i) {
+    return tx_letter((uint32_t)(w[i >> 5] >> (2u * (i & 31u))) & 3u, (m[i >> 5] >> (i & 31u)) & 1u);
+}
+// four letters from four 2-bit codes (c8) and their four N bits
+CF_DEV uint32_t tx_letters4(uint32_t c8, uint32_t m4) {
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t d = 0; d < 4; d++) v |= tx_letter((c8 >> (2u * d)) & 3u, (m4 >> d) & 1u) << (8u * d);
+    return v;
+}
+// the n bases of a read (w, m: its packed words and N masks) as A C G T N: a lane takes 16 bases at a time — one 32-bit stretch of
+// the 2-bit codes, expanded in registers into four dwords of letters
+CF_DEV void fmt_wave_seq(uint8_t *dst, uint32_t at, const uint64_t *w, const uint32_t *m, uint32_t n, uint32_t lane) {
+    uint32_t head = (4u - (at & 3u)) & 3u;
+    if (head > n) head = n;
+    const uint32_t mid = (n - head) >> 2, tail = (n - head) & 3u;
+    for (uint32_t i = lane; i < head; i += CF_WAVE) dst[i] = (uint8_t)tx_base_at(w, m, i);
+    for (uint32_t j = lane; 4 * j < mid; j += CF_WAVE) {
+        const uint32_t b = head + 16 * j, k = b >> 5, s = b & 31u;
+        uint64_t c = w[k] >> (2u * s);
+        uint32_t mm = m[k] >> s;
+        if (s > 16u && 32u * (k + 1) < n) { c |= w[k + 1] << (64u - 2u * s); mm |= m[k + 1] << (32u - s); }   // (the 16 bases lie in two words)
+#pragma unroll
+        for (uint32_t d = 0; d < 4; d++)
+            if (4 * j + d < mid) {
+                const uint32_t v = tx_letters4((uint32_t)(c >> (8u * d)) & 0xffu, (mm >> (4u * d)) & 0xfu);
+                __builtin_memcpy(__builtin_assume_aligned(dst + b + 4 * d, 4), &v, 4);
+            }
+    }
+    for (uint32_t i = head + 4 * mid + lane; i < head + 4 * mid + tail; i += CF_WAVE) dst[i] = (uint8_t)tx_base_at(w, m, i);
+}
+// the long column c of query Q at dst
+CF_DEV void fmt_wave_long(const DTextFmt &f, const FmtQuery &Q, uint32_t c, uint8_t *dst, uint32_t at, uint32_t lane) {
+    const bool both = c == kColSeq || c == kColQual, second = c == kColSeq2 || c == kColQual2;
+    if (second && !f.paired) return;
+    for (uint32_t part = second ? 1u : 0u; part < (both && f.paired ? 2u : second ? 2u : 1u); part++) {
+        const uint32_t r = Q.ra + part, n = part ? Q.len2 : Q.len1;
+        if (part && both) { if (lane == 0) dst[0] = '_'; dst++; at++; }
+        if (tx_col_qual(c)) fmt_wave_bytes(dst, at, f.qualOff ? f.text : nullptr, f.qualOff ? f.qualOff[r] : 0u, n, lane);
+        else fmt_wave_seq(dst, at, f.bases + f.woff[r], f.nmask + f.woff[r], n, lane);
+        dst += n; at += n;
+    }
+}
+CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t q, uint8_t *lds = nullptr) {
+#ifndef CF_HOST_EMU
+    if (!lds) lds = fmt_wave_lds();
+#endif
+    const bool live = q < f.nQueries;
+    uint32_t oneTaxon = 0xffffffffu;                                     // the taxon this query is a perfect single assignment of
+    const uint32_t lane = cf_lane(), q0 = q - lane;
+    const uint32_t qe = q0 + CF_WAVE < f.nQueries ? q0 + CF_WAVE : f.nQueries;
+    const uint64_t segBegin = q0 < f.nQueries ? f.outOff[q0] : 0, segEnd = q0 < f.nQueries ? f.outOff[qe] : 0;
+    const uint32_t phase = (uint32_t)(segBegin & 3u);
+    const bool viaLds = lds != nullptr && segEnd > segBegin && segEnd - segBegin + phase <= kFmtLds && segEnd <= f.outCap;
+    bool anyLong = false;
+    for (uint32_t k = 0; k < pc.nCols; k++) anyLong = anyLong || tx_col_long(pc.col[k]);
+    bool printed = false;
+    if (live) {
+        const FmtQuery Q = fmt_query(f, q);
+        const bool uncl = Q.n == 0;
+        const uint32_t ms = f.maxScore[q];
+        const uint64_t o = f.outOff[q];
+        printed = o + f.size[q] <= f.outCap;
+        if (printed) {
+            uint8_t *w = viaLds ? lds + phase + (uint32_t)(o - segBegin) : f.out + o;
+            for (uint32_t i = 0; i < (uncl ? 1u : Q.n); i++) {
+                const TextRow row = uncl ? TextRow{0, 0, 0, 0} : f.rows[Q.f0 + i];
+                for (uint32_t k = 0; k < pc.nCols; k++) { w = fmt_col_put(f, Q, pc.col[k], uncl, row, w); *w++ = k + 1 < pc.nCols ? '\t' : '\n'; }
+            }
+        }
+        // SpeciesMetrics::addSpeciesCounts (aln_sink.h:142-172), as in fmt_write_body: the tally does not depend on the columns
+        if (uncl) oneTaxon = f.idxZero;
+        else if (Q.n == 1) { const TextRow row = f.rows[Q.f0]; if (ms != 0xffffffffu && row.score >= ms && row.tidx < f.nTaxa) oneTaxon = row.tidx; }
+        else {
+            bool all = ms != 0xffffffffu;
+            for (uint32_t i = 0; i < Q.n && all; i++) { const TextRow row = f.rows[Q.f0 + i]; all = row.score >= ms && row.tidx < f.nTaxa; }
+            if (all) {
+                const uint32_t at = cf_atomic_add(&f.st->tupleWords, Q.n + 1);
+                if (at + Q.n + 1 <= f.tuplesCap) { f.tuples[at] = Q.n; for (uint32_t i = 0; i < Q.n; i++) f.tuples[at + 1 + i] = f.rows[Q.f0 + i].tidx; }
+            }
+        }
+    }
+    if (anyLong) {
+        // the long fields, query by query: the ballot names the lanes whose rows are being printed; what the field needs — where its
+        // letters come from, where they go, how many — is the same for every lane (read again from the leading lane's query)
+        uint64_t pend = cf_ballot(printed);
+        while (pend) {
+            const uint32_t ql = q0 + (uint32_t)cf_ctz64(pend);
+            pend &= pend - 1;
+            const FmtQuery Q = fmt_query(f, ql);
+            const bool uncl = Q.n == 0;
+            uint64_t o = f.outOff[ql];
+            for (uint32_t i = 0; i < (uncl ? 1u : Q.n); i++) {
+                const TextRow row = uncl ? TextRow{0, 0, 0, 0} : f.rows[Q.f0 + i];
+                for (uint32_t k = 0; k < pc.nCols; k++) {
+                    const uint32_t c = pc.col[k], n = fmt_col_len(f, Q, c, uncl, row);
+                    if (tx_col_long(c) && n) fmt_wave_long(f, Q, c, viaLds ? lds + phase + (uint32_t)(o - segBegin) : f.out + o, (uint32_t)(o & 3u), lane);
+                    o += n + 1;
+                }
+            }
+        }
+    }
+    if (viaLds) {
+        // (as in fmt_write_body) every lane's bytes are in LDS: out they go, dword j of the stretch by lane j mod 64
         cf_compiler_fence();
         const uint32_t total = phase + (uint32_t)(segEnd - segBegin);
         uint8_t *const dst = f.out + (segBegin - phase);                  // a dword boundary of the output

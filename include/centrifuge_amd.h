@@ -313,8 +313,8 @@ typedef struct {
     uint32_t irregular;        /* 0 = the slot holds the block's reads; else why the block is not in the plain form (a bit set) */
 } cf_text_info;
 cf_status cf_batch_upload_text(cf_batch *, const cf_text_reads *, void *hip_stream, cf_text_info *info);
-/* Out: the batch's rows as the text centrifuge prints by default — readID seqID taxID score 2ndBestScore hitLength queryLength
- * numMatches, one line per row, query order — formatted on the device from the rows the kernels left there (no row crosses the
+/* Out: the batch's rows as text — by default the columns centrifuge prints by default, readID seqID taxID score 2ndBestScore
+ * hitLength queryLength numMatches; any other list after cf_batch_set_text_columns —, one line per row, query order, formatted on the device from the rows the kernels left there (no row crosses the
  * link) with the readIDs copied out of the uploaded block; in the slot's pinned memory, valid until its next upload.  Needs the
  * slot in the narrow result format and a batch that came through cf_batch_upload_text; replaces cf_batch_wait.  The same pass
  * tallies what the report needs beyond the device's per-taxon counters (cf_counts_get): the perfect single assignments per taxon
@@ -329,6 +329,38 @@ typedef struct {
     uint32_t row_passes, slow_post, slow_score;
 } cf_results_text;
 cf_status cf_batch_wait_text(cf_batch *, cf_results_text *out);
+/* Which columns cf_batch_wait_text prints: any list --tab-fmt-cols / --out-fmt sam can name (centrifuge.cpp:484-520), formatted
+ * on the device like the default eight — taxRank / taxName from per-taxon string tables made at the first program that names
+ * them, readSeq* from the batch's packed words as A C G T N (never copied from the uploaded text, which may be wrapped or lower
+ * case), readQual* from the uploaded block's quality lines (FASTA: 'I' throughout); readSeq / readQual of mates are seq1_seq2,
+ * readSeq2 / readQual2 are empty for unpaired reads; an unclassified read prints seqID "unclassified", taxID, score and hitLength
+ * 0, and tax ID 0's rank and name.  The tally (cf_results_text::tuples, cf_counts_get_single) does not depend on the columns. */
+#define CF_COL_READ_ID      0
+#define CF_COL_SEQ_ID       1
+#define CF_COL_TAX_ID       2
+#define CF_COL_TAX_RANK     3
+#define CF_COL_TAX_NAME     4
+#define CF_COL_SCORE        5
+#define CF_COL_SCORE2       6
+#define CF_COL_HIT_LEN      7
+#define CF_COL_QUERY_LEN    8
+#define CF_COL_NUM_MATCHES  9
+#define CF_COL_SEQ         10
+#define CF_COL_QUAL        11
+#define CF_COL_SEQ1        12
+#define CF_COL_QUAL1       13
+#define CF_COL_SEQ2        14
+#define CF_COL_QUAL2       15
+#define CF_COL_PLACEHOLDER 16   /* prints *0 (SAM's CIGAR; aln_sink.h:2322-2324) */
+#define CF_COL_ZERO        17   /* prints 0  (SAM's FLAG, POS, MAPQ, PNEXT)      */
+#define CF_TEXT_MAX_COLS 32
+/* a column's name as the reference spells it (every alias, the SAM field names included) -> its code, or -1 */
+int32_t   cf_text_column_of(const char *name);
+/* The slot's column program for its LATER cf_batch_wait_text calls.  n_cols == 0 restores the default eight; a slot that never
+ * calls this prints them, through the same kernels as before.  More than CF_TEXT_MAX_COLS columns or an unknown code: CF_ERR_ARG
+ * (cf_last_error says which), and the slot keeps the program it had.  The program may change between batches; a change after a
+ * batch's first cf_batch_wait_text does NOT format that batch again — its text is kept, and a second wait returns it as it is. */
+cf_status cf_batch_set_text_columns(cf_batch *, const int32_t *cols, uint32_t n_cols);
 
 /* pinned (page-locked) host memory: what makes the transfers of the async calls truly asynchronous */
 cf_status cf_host_alloc(void **p, size_t bytes);
@@ -423,8 +455,8 @@ cf_status cf_batch_opcounts(cf_batch *, cf_opcounts *);
 /* ------------------------------------------------------------- counters
  * Dense per-taxon {n_reads, n_unique_reads} (ReadCounts aln_sink.h:45-51),
  * length cf_index_num_taxa each, accumulated on the device by cf_classify.
- * cf_counts_device exposes the device buffer (2*num_taxa u64: n_reads then
- * n_unique) so a caller can all-reduce it in place with RCCL across the
+ * cf_counts_device exposes the device buffer (3*num_taxa u64: n_reads, then
+ * n_unique, then the perfect single assignments) so a caller can all-reduce it in place with RCCL across the
  * per-GPU processes of a node (the only collective of the path). */
 cf_status cf_counts_reset(cf_classifier *);
 cf_status cf_counts_get(cf_classifier *, uint64_t *n_reads, uint64_t *n_unique);
@@ -433,7 +465,7 @@ cf_status cf_counts_get(cf_classifier *, uint64_t *n_reads, uint64_t *n_unique);
 cf_status cf_counts_get_single(cf_classifier *, uint64_t *n_single);
 void     *cf_counts_device(cf_classifier *);
 /* The path's only collective: in-place sum of the counters over the ranks of
- * an RCCL communicator — ncclAllReduce(counts, counts, 2*num_taxa, ncclUint64, ncclSum, comm,
+ * an RCCL communicator — ncclAllReduce(counts, counts, 3*num_taxa, ncclUint64, ncclSum, comm,
  * stream), enqueued on `stream` (hipStream_t or NULL).  `nccl_comm` is an ncclComm_t the caller
  * created (ncclCommInitRank, one process per GPU).  librccl is bound at first use (dlopen), so
  * the library itself carries no link-time RCCL dependency.  Replaces the mutexed
