@@ -85,6 +85,17 @@ class TextInfo(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("max_len", C.c_uint32), ("irregular", C.c_uint32)]
 
 
+class BgzfReads(C.Structure):
+    """cf_bgzf_reads of include/centrifuge_amd.h"""
+    _fields_ = [("members", C.c_void_p), ("n_bytes", C.c_uint64), ("head", C.c_void_p), ("head_bytes", C.c_uint64),
+                ("format", C.c_int32), ("global_seed", C.c_uint32), ("max_reads", C.c_uint64), ("last", C.c_int32)]
+
+
+class BgzfInfo(C.Structure):
+    """cf_bgzf_info of include/centrifuge_amd.h"""
+    _fields_ = [("tail", C.c_void_p), ("tail_bytes", C.c_uint64), ("inflated_bytes", C.c_uint64), ("corrupt", C.c_uint32), ("bad_member", C.c_uint32)]
+
+
 class ResultsText(C.Structure):
     """cf_results_text of include/centrifuge_amd.h"""
     _fields_ = [("text", C.c_void_p), ("n_bytes", C.c_uint64), ("tuples", C.c_void_p), ("n_tuple_words", C.c_uint64),
@@ -146,7 +157,7 @@ EXPORTS = [
     "cf_batch_max_scores", "cf_report_create", "cf_report_destroy", "cf_report_add", "cf_report_add_narrow", "cf_report_add_counts", "cf_report_reset_counts", "cf_report_write", "cf_report_serialize", "cf_report_merge",
     "cf_index_text_verify_rate", "cf_index_text_verify_build_ms", "cf_index_wide_ftab_chars", "cf_index_occ_planes", "cf_index_occ_planes_build_ms", "cf_index_resolve_rate", "cf_index_resolve_build_ms", "cf_index_walk_bound", "cf_index_resolve_by_position", "cf_slot_estimate_bytes", "cf_batch_reclassify_async", "cf_comm_init_all", "cf_comm_destroy", "cf_counts_allreduce_group", "cf_stream_create", "cf_stream_destroy", "cf_device_count", "cf_device_numa_node", "cf_thread_bind_near_device",
     "cf_report_adopt_counts", "cf_debug_scan", "cf_host_alloc", "cf_host_free", "cf_batch_alloc", "cf_batch_upload_packed_async", "cf_classify_async", "cf_batch_download_async",
-    "cf_batch_submit", "cf_batch_wait", "cf_batch_upload", "cf_batch_set_limits",
+    "cf_batch_submit", "cf_batch_wait", "cf_batch_upload", "cf_batch_set_limits", "cf_batch_upload_bgzf",
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
 ]
@@ -216,6 +227,7 @@ def lib():
         "cf_results_narrow_expand": (i32, [vp, C.POINTER(ResultsNarrow), vp, C.c_uint32, i32, vp, vp, vp]),
         "cf_batch_upload": (i32, [vp, vp, vp, vp, u64, i32, vp]),
         "cf_batch_upload_text": (i32, [vp, C.POINTER(TextReads), vp, C.POINTER(TextInfo)]),
+        "cf_batch_upload_bgzf": (i32, [vp, C.POINTER(BgzfReads), vp, C.POINTER(TextInfo), C.POINTER(BgzfInfo)]),
         "cf_batch_wait_text": (i32, [vp, C.POINTER(ResultsText)]),
         "cf_text_column_of": (C.c_int32, [cp]), "cf_batch_set_text_columns": (i32, [vp, vp, u32]),
         "cf_counts_get_single": (i32, [vp, vp]),
@@ -611,6 +623,23 @@ class Slot:
         if not info.irregular:
             _check(self.L.cf_classify_async(self.clf.h, self.h, stream))
         return info
+
+    def submit_bgzf(self, members, fmt, head=b"", last=False, seed=0, max_reads=0, stream=None):
+        """whole BGZF members as the file holds them (cf_batch_upload_bgzf: inflated and parsed on the device; head = the tail the
+        call before returned), then the kernels.  -> tail (bytes: the text behind the last whole record), TextInfo, BgzfInfo;
+        info.irregular != 0 or zinfo.corrupt != 0: nothing was submitted (the tail is None)"""
+        buf = np.frombuffer(members, dtype=np.uint8) if len(members) else np.zeros(1, dtype=np.uint8)
+        hbuf = np.frombuffer(head, dtype=np.uint8) if len(head) else np.zeros(1, dtype=np.uint8)
+        br, info, zinfo = BgzfReads(), TextInfo(), BgzfInfo()
+        br.members, br.n_bytes, br.head, br.head_bytes = buf.ctypes.data, len(members), hbuf.ctypes.data, len(head)
+        br.format, br.global_seed, br.max_reads, br.last = int(fmt), int(seed), int(max_reads), int(bool(last))
+        self._keep = (buf, hbuf, br)
+        _check(self.L.cf_batch_upload_bgzf(self.h, C.byref(br), stream, C.byref(info), C.byref(zinfo)))
+        if info.irregular or zinfo.corrupt:
+            return None, info, zinfo
+        tail = C.string_at(zinfo.tail, zinfo.tail_bytes) if zinfo.tail_bytes else b""
+        _check(self.L.cf_classify_async(self.clf.h, self.h, stream))
+        return tail, info, zinfo
 
     def set_text_columns(self, cols):
         """the columns later wait_text() calls print: names (as --tab-fmt-cols spells them) or COL_* codes; [] = the default eight"""

@@ -23,6 +23,7 @@ struct ByteSource::Impl {
     virtual ~Impl() = default;
     virtual size_t read(char *dst, size_t n) = 0;
     virtual int fd() const { return -1; }
+    virtual int bgzfFd() const { return -1; }
 };
 
 namespace {
@@ -110,6 +111,7 @@ struct BgzfImpl : ByteSource::Impl {
     bool eof = false;
     BgzfImpl(std::FILE *f_, std::string p, int t) : f(f_), path(std::move(p)), threads(std::max(1, t)), out(kBatch * kSlot) {}
     ~BgzfImpl() override { if (f) std::fclose(f); }
+    int bgzfFd() const override { return fileno(f); }
 
     [[noreturn]] void bad(const char *what) { throw std::runtime_error("Error: \"" + path + "\": " + what); }
 
@@ -236,7 +238,7 @@ struct SpawnImpl : ByteSource::Impl {
 
 }  // namespace
 
-ByteSource::ByteSource(const std::string &path, int threads) {
+ByteSource::ByteSource(const std::string &path, int threads, uint64_t bgzfStart) {
     if (path == "-") { impl_.reset(new PlainImpl(stdin, false, path)); return; }
     if (endsWith(path, ".bz2")) {
         std::FILE *probe = std::fopen(path.c_str(), "rb");
@@ -252,7 +254,10 @@ ByteSource::ByteSource(const std::string &path, int threads) {
         const size_t got = std::fread(h, 1, 16, f);
         std::rewind(f);
         const bool bgzf = got == 16 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0;
-        if (bgzf) impl_.reset(new BgzfImpl(f, path, threads));
+        if (bgzf) {
+            if (bgzfStart && fseeko(f, (off_t)bgzfStart, SEEK_SET) != 0) { std::fclose(f); cannotOpen(path); }
+            impl_.reset(new BgzfImpl(f, path, threads));
+        }
         else impl_.reset(new GzImpl(f, path));
         return;
     }
@@ -265,6 +270,15 @@ size_t ByteSource::read(char *dst, size_t n) { return impl_->read(dst, n); }
 
 bool ByteSource::regularFile(int &fd, uint64_t &size) const {
     const int d = impl_->fd();
+    if (d < 0) return false;
+    struct stat st;
+    if (fstat(d, &st) != 0 || !S_ISREG(st.st_mode)) return false;
+    fd = d; size = (uint64_t)st.st_size;
+    return true;
+}
+
+bool ByteSource::bgzfFile(int &fd, uint64_t &size) const {
+    const int d = impl_->bgzfFd();
     if (d < 0) return false;
     struct stat st;
     if (fstat(d, &st) != 0 || !S_ISREG(st.st_mode)) return false;

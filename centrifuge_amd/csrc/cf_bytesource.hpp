@@ -15,7 +15,8 @@ namespace cfamd {
 class ByteSource {
 public:
     // threads: helper threads a BGZF input may use for inflating blocks (>= 1)
-    explicit ByteSource(const std::string &path, int threads = 1);
+    // bgzfStart: a BGZF file is read from the member that starts at this byte of it (other inputs: ignored)
+    explicit ByteSource(const std::string &path, int threads = 1, uint64_t bgzfStart = 0);
     ~ByteSource();
     ByteSource(const ByteSource &) = delete;
     ByteSource &operator=(const ByteSource &) = delete;
@@ -24,6 +25,9 @@ public:
     // A plain regular file: its descriptor and size, so that a caller may pread() ranges of it from several threads
     // (read() must then not be used any more); false for stdin, pipes and compressed inputs.
     bool regularFile(int &fd, uint64_t &size) const;
+    // A regular file whose first member is BGZF: its descriptor and size, so that a caller may pread() whole members of it
+    // (cf_batch_upload_bgzf inflates them on the device); read() stays usable.
+    bool bgzfFile(int &fd, uint64_t &size) const;
 
     struct Impl;
 

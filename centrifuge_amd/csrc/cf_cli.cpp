@@ -92,7 +92,9 @@ void usage(std::FILE *f) {
         "          all-reduced with RCCL, output in input order)  --gpu-list <d,..>  --slots <int> (batches in flight per device, 2)\n"
         "          --host-io (reads are parsed and rows printed by host threads for every input; default: plain FASTA / FASTQ files go up as\n"
         "          text and the rows come back as text, formatted on the device — the default columns, any --tab-fmt-cols list of up\n"
-        "          to 32 columns, --out-fmt sam — same bytes either way)\n"
+        "          to 32 columns, --out-fmt sam — same bytes either way; an unpaired BGZF .gz file (bgzip, htslib) goes up compressed and\n"
+        "          is inflated on the device, the parser pool taking the file over at its first record outside the plain form; mates,\n"
+        "          other .gz files, .bz2, stdin, -s and -5/-3 keep the host threads)\n"
         " Index:   --hbm-budget-gb <float> (device memory the index may take, files + derived tables; default: what is free less a\n"
         "          reserve for the batch slots)  --small-range-rows <-1|0|2..15> (search ranges of up to that many rows are finished\n"
         "          against the text; 0 = decided from how repeat-rich the indexed collection is, -1 = off; results do not depend on it)\n"
@@ -256,6 +258,9 @@ struct Batch {
     uint64_t tOff2 = 0, tLen2 = 0;
     const std::string *tPath2 = nullptr;
     ReadSoA r2;                                       // ... and its reads when the host parser takes the block
+    // ... or a run of whole BGZF members of a .gz file (tOff, tLen: the compressed bytes) that are inflated on the device (classifyBgzf)
+    bool tBgzf = false;
+    uint64_t tMembers = 0;
 };
 
 // Numbers handed in by position (the blocks of an input in file order), each caller learning the sum of all earlier positions:
@@ -342,6 +347,8 @@ struct GpuThread {
     char *tin = nullptr;                            // the device text path: the block as the file holds it, in pinned memory
     size_t tinCap = 0;
     uint64_t textBlocks = 0, hostBlocks = 0;        // blocks that went up as text / were parsed on the host (not in the plain form)
+    uint64_t zMembers = 0;                          // BGZF members this thread had inflated on the device
+    std::string zHead;                              // the text in front of the run in hand (the tail of the run before it)
 };
 
 struct Runner {
@@ -375,6 +382,13 @@ struct Runner {
     std::atomic<bool> uptoReached{false};           // -u: the blocks so far hold that many reads
     std::atomic<uint64_t> textBatches{0};           // batches whose rows were formatted (and tallied) on the device
     std::vector<OutBuf *> hostOut;                  // per GPU thread: the text of a block that was parsed and formatted on the host
+    // BGZF members inflated on the device: the runs of a file hand the text behind their last whole record on in file order (the one
+    // serial step between the GPU threads); the first run the device refuses ends the way, and the parser pool takes the file over there
+    OrderedSum tailChain;
+    std::string zTail;                              // the tail of the last run that went through (guarded by tailChain's turn)
+    bool zStopped = false;                          // a run was refused: the runs behind it do nothing
+    uint64_t zResumeOff = 0;                        // ... the byte of the file its first member starts at
+    std::string zResumeHead, zWhy;                  // ... the text in front of that member, and what the device said
 
     ~Runner() {                                     // error paths leave through here as well
         try { waitWrite(); } catch (...) {}          // (a run that ends on an error: the writer must be done with the file before it is closed)
@@ -801,6 +815,77 @@ struct Runner {
         b.nq = 0;                                          // (the output stage has nothing left to do for this batch)
     }
 
+    // A run of whole BGZF members on one GPU thread: the compressed bytes into the thread's pinned buffer and up as they are
+    // (cf_batch_upload_bgzf: inflated, cut behind the last whole record and parsed on the device) with the tail of the run before
+    // in front; the tail that comes back is handed on at once, and only then the kernels, the rows as text and the write follow —
+    // they overlap with the next run's upload.  A run the device refuses (a record outside the plain form, a corrupt member, a
+    // tail beyond the slot's room) ends the way for the file: the producer hands the rest to the parser pool, from this run's first member.
+    void classifyBgzf(Batch &b, GpuThread &g) {
+        auto t0 = std::chrono::steady_clock::now();
+        auto lap = [&](double &acc) { const auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(t - t0).count(); t0 = t; };
+        if (b.tLen + 64 > g.tinCap) {
+            if (g.tin) cf_host_free(g.tin);
+            g.tin = nullptr; g.tinCap = 0;
+            void *q = nullptr;
+            const size_t want = (size_t)(b.tLen + b.tLen / 8 + 4096);
+            CF_TRY(cf_host_alloc(&q, want));
+            g.tin = static_cast<char *>(q); g.tinCap = want;
+        }
+        readFileRange(b.tFd, g.tin, (size_t)b.tLen, b.tOff, *b.tPath);
+        lap(g.tm.read);
+        CF_TRY(cf_batch_set_result_format(g.slot, CF_RESULTS_NARROW));
+        cf_bgzf_reads in{};
+        in.members = g.tin; in.n_bytes = b.tLen; in.format = o.format == ReadFormat::Fasta ? CF_TEXT_FASTA : CF_TEXT_FASTQ;
+        in.global_seed = o.seed; in.max_reads = 0; in.last = b.tLast ? 1 : 0;
+        cf_text_info info{};
+        cf_bgzf_info zi{};
+        (void)tailChain.enter(b.tIdx);
+        bool skip = zStopped;
+        if (!skip) {
+            g.zHead = zTail;
+            in.head = g.zHead.data(); in.head_bytes = g.zHead.size();
+            const cf_status st = cf_batch_upload_bgzf(g.slot, &in, g.stream, &info, &zi);
+            // (a text beyond the batch's 32-bit places is refused before anything is uploaded: the host path has no such limit)
+            if (st != CF_OK && st != CF_ERR_ARG) { tailChain.fail(); die(std::string("centrifuge-class: ") + cf_strerror(st) + ": " + cf_last_error()); }
+            if (st != CF_OK || info.irregular || zi.corrupt) {
+                zStopped = true; zResumeOff = b.tOff; zResumeHead = g.zHead;
+                zWhy = zi.corrupt ? "a corrupt member" : st != CF_OK ? "a run beyond the batch's size" : "a record outside the plain form";
+                skip = true;
+            } else zTail.assign(zi.tail, (size_t)zi.tail_bytes);
+        }
+        tailChain.leave(0);
+        lap(g.tm.parse);
+        const uint64_t nReads = skip ? 0 : info.n_reads;
+        const uint64_t base = readChain.enter(b.tIdx);
+        readChain.leave(nReads);
+        const uint64_t take = base >= o.upto ? 0 : std::min<uint64_t>(nReads, o.upto - base);
+        if (!skip && base + nReads >= o.upto) uptoReached = true;
+        const char *text = "";
+        uint64_t nText = 0;
+        if (take) {
+            if (take < nReads) {                                        // the run -u ends in: once more, its first reads only
+                in.max_reads = take;
+                CF_TRY(cf_batch_upload_bgzf(g.slot, &in, g.stream, &info, &zi));
+                if (info.irregular || zi.corrupt || info.n_reads != take) die("internal error: a run of members changed between two uploads");
+            }
+            CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
+            lap(g.tm.create);
+            cf_results_text res{};
+            CF_TRY(cf_batch_wait_text(g.slot, &res));
+            lap(g.tm.classify);
+            if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
+            text = res.text; nText = res.n_bytes;
+            textBatches++; g.textBlocks++;
+            lap(g.tm.report);
+        }
+        if (!skip) g.zMembers += b.tMembers;
+        const uint64_t at = outChain.enter(b.tIdx);
+        if (outRegular) { outChain.leave(nText); if (nText) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
+        else { try { if (nText) writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
+        lap(g.tm.write);
+        b.nq = 0;
+    }
+
     // the report file with its stderr lines (centrifuge.cpp:3134-3141,3231-3319; aln_sink.h:471-472)
     template <typename Hms>
     void writeReport(cf_report *r, const std::string &path, const Hms &hms) {
@@ -1114,7 +1199,7 @@ int run(int argc, const char **argv) {
                     queue.pop_front();
                 }
                 cv.notify_all();
-                if (b->endOfInput < 0) { if (b->isText) R.classifyText(*b, g, wi); else R.classify(*b, g); }
+                if (b->endOfInput < 0) { if (b->isText && b->tBgzf) R.classifyBgzf(*b, g); else if (b->isText) R.classifyText(*b, g, wi); else R.classify(*b, g); }
                 {
                     std::lock_guard<std::mutex> lk(mu);
                     const uint64_t sq = b->seq;
@@ -1124,7 +1209,7 @@ int run(int argc, const char **argv) {
             }
         } catch (const std::exception &e) {
             { std::lock_guard<std::mutex> lk(mu); if (workerError.empty()) workerError = e.what(); }
-            R.readChain.fail(); R.outChain.fail();           // (threads waiting for this one's block must not wait for ever)
+            R.readChain.fail(); R.outChain.fail(); R.tailChain.fail();           // (threads waiting for this one's block must not wait for ever)
         }
         { std::lock_guard<std::mutex> lk(mu); gpuRunning--; }
         cv.notify_all();
@@ -1171,6 +1256,7 @@ int run(int argc, const char **argv) {
     };
     auto ts = std::chrono::steady_clock::now();
     uint64_t benchReads = 0, benchBases = 0;
+    uint64_t zHostMembers = 0;                         // BGZF members of files that began on the device and were left to the parser pool
     try {
       size_t lastSeq = 0, lastNames = 0, lastReads = 0;
       bool lastQual = false, aborted = false;
@@ -1178,7 +1264,8 @@ int run(int argc, const char **argv) {
         const Input &in = inputs[fi];
         const bool paired = in.paired;
         struct stat isb;
-        uint64_t resume1 = 0, resume2 = 0, resumeId = 0;              // where the parser pool takes over from the text path (mates only)
+        uint64_t resume1 = 0, resume2 = 0, resumeId = 0;              // where the parser pool takes over from the text path (mates, BGZF files)
+        std::string resumeHead;                                       // ... a BGZF file: the text in front of the member at resume1
         if (R.textCapable && paired && !o.dumpReads && in.f1 != "-" && in.f2 != "-" && ::stat(in.f1.c_str(), &isb) == 0 && S_ISREG(isb.st_mode) &&
             ::stat(in.f2.c_str(), &isb) == 0 && S_ISREG(isb.st_mode)) {
             // Mates on the device text path: the first file is cut like an unpaired one; the second where it holds as many records
@@ -1243,7 +1330,7 @@ int run(int argc, const char **argv) {
                     if (!b) b = std::make_unique<Batch>();
                     b->nq = 0; b->endOfInput = -1; b->paired = true; b->narrowRows = false;
                     b->isText = true; b->tFd = fd1; b->tOff = pos1; b->tLen = cut1 - pos1; b->tFirst = pos1 == 0; b->tLast = cut1 == fs1; b->tIdx = idx++; b->tPath = &in.f1;
-                    b->tFd2 = fd2; b->tOff2 = pos2; b->tLen2 = end2 - pos2; b->tPath2 = &in.f2;
+                    b->tFd2 = fd2; b->tOff2 = pos2; b->tLen2 = end2 - pos2; b->tPath2 = &in.f2; b->tBgzf = false;
                     pos1 = cut1; pos2 = end2; pairs += n;
                     const auto tp1 = std::chrono::steady_clock::now();
                     R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
@@ -1283,7 +1370,7 @@ int run(int argc, const char **argv) {
                     if (!b) b = std::make_unique<Batch>();
                     b->nq = 0; b->endOfInput = -1; b->paired = false; b->narrowRows = false;
                     b->isText = true; b->tFd = fd; b->tOff = pos; b->tLen = cut - pos; b->tFirst = pos == 0; b->tLast = cut == fsize; b->tIdx = idx++; b->tPath = &in.f1;
-                    b->tFd2 = -1; b->tLen2 = 0;
+                    b->tFd2 = -1; b->tLen2 = 0; b->tBgzf = false;
                     pos = cut;
                     const auto tp1 = std::chrono::steady_clock::now();
                     R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
@@ -1296,6 +1383,74 @@ int run(int argc, const char **argv) {
                 if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
                 continue;
             }
+            const bool devInflate = !(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE")));
+            if (devInflate && src.bgzfFile(fd, fsize) && fsize) {
+                // A BGZF file: its members are hopped here by their headers (BgzfImpl::fill's test) and dealt out as runs of whole
+                // members, CF_TEXT_BLOCK bytes of compressed plus inflated size at most; the GPU threads have them inflated on the
+                // device.  Where a header is not BGZF's, or at the first run the device refuses, the parser pool takes the rest.
+                if (!drain()) { aborted = true; break; }
+                R.waitWrite();
+                std::fflush(R.out);
+                R.outFd = fileno(R.out);
+                struct stat sb;
+                R.outRegular = ::fstat(R.outFd, &sb) == 0 && S_ISREG(sb.st_mode);
+                R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
+                R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
+                R.outMap = false;
+                R.readChain.reset(); R.outChain.reset(); R.tailChain.reset(); R.uptoReached = false;
+                R.zTail.clear(); R.zStopped = false; R.zResumeHead.clear(); R.zWhy.clear();
+                const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
+                void *zm = ::mmap(nullptr, (size_t)fsize, PROT_READ, MAP_SHARED, fd, 0);
+                if (zm == MAP_FAILED) die("Error: could not map \"" + in.f1 + "\"");
+                struct Unmap { void *a; size_t n; ~Unmap() { ::munmap(a, n); } } unmap{zm, (size_t)fsize};
+                const unsigned char *z = static_cast<const unsigned char *>(zm);
+                // a member's size in the file and the size of its text; false: not a BGZF member (or one cut short)
+                auto member = [&](uint64_t at, uint64_t &bsize, uint64_t &isize) {
+                    if (fsize - at < 18) return false;
+                    const unsigned char *h = z + at;
+                    const uint64_t xlen = (uint64_t)(h[10] | (h[11] << 8));
+                    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || xlen < 6 || h[12] != 'B' || h[13] != 'C' || h[14] != 2 || h[15] != 0) return false;
+                    bsize = (uint64_t)(h[16] | (h[17] << 8)) + 1;
+                    if (bsize < 12 + xlen + 8 || bsize > fsize - at) return false;
+                    uint32_t v; std::memcpy(&v, h + bsize - 4, 4);
+                    isize = v;
+                    return isize <= 65536;
+                };
+                uint64_t pos = 0, idx = 0;
+                bool badHeader = false;
+                while (pos < fsize && !R.uptoReached && !badHeader) {
+                    const auto tp0 = std::chrono::steady_clock::now();
+                    uint64_t end = pos, bytes = 0, nMem = 0, bs = 0, is = 0;
+                    while (end < fsize) {
+                        if (!member(end, bs, is)) { badHeader = true; break; }
+                        if (nMem && bytes + bs + is > kBlock) break;
+                        bytes += bs + is; end += bs; nMem++;
+                    }
+                    if (!nMem) break;
+                    std::unique_ptr<Batch> b;
+                    { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
+                    if (!b) b = std::make_unique<Batch>();
+                    b->nq = 0; b->endOfInput = -1; b->paired = false; b->narrowRows = false;
+                    b->isText = true; b->tBgzf = true; b->tMembers = nMem; b->tFd = fd; b->tOff = pos; b->tLen = end - pos; b->tFirst = pos == 0; b->tLast = end == fsize; b->tIdx = idx++; b->tPath = &in.f1;
+                    b->tFd2 = -1; b->tLen2 = 0;
+                    pos = end;
+                    const auto tp1 = std::chrono::steady_clock::now();
+                    R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
+                    if (!submit(std::move(b))) { aborted = true; break; }
+                    R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+                    { std::lock_guard<std::mutex> lk(R.tailChain.mu); if (R.zStopped) break; }       // (no run behind a refused one is of use)
+                }
+                if (aborted || !drain()) { aborted = true; break; }
+                if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
+                if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
+                if (R.uptoReached || (!R.zStopped && pos >= fsize)) continue;
+                // the parser pool goes on: from the refused run's first member with that run's head in front, or from the bytes that are no member
+                resume1 = R.zStopped ? R.zResumeOff : pos;
+                resumeHead = R.zStopped ? R.zResumeHead : R.zTail;
+                resumeId = R.readChain.sum;
+                uint64_t bs = 0, is = 0;
+                for (uint64_t at = resume1; at < fsize && member(at, bs, is); at += bs) zHostMembers++;
+            }
         }
         // single-end chunks travel whole (they become the batch): the parser threads also make their packed form; mates are
         // interleaved into the batch pair by pair, their packed words along with their bytes (every read starts on a word).
@@ -1303,7 +1458,7 @@ int run(int argc, const char **argv) {
         // the knob CF_DUMP_FROM_PACKED=1 prints the bases back out of the packed form — the tests' window on it.)
         const bool dumpPacked = o.dumpReads && cfamd::cf_knob("CF_DUMP_FROM_PACKED") && std::atoi(cfamd::cf_knob("CF_DUMP_FROM_PACKED"));
         const bool wantPacked = o.dumpReads ? dumpPacked : !(cfamd::cf_knob("CF_CLI_PACKED") && !std::atoi(cfamd::cf_knob("CF_CLI_PACKED")));
-        ChunkedReader s1({in.f1}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume1);
+        ChunkedReader s1({in.f1}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume1, resumeHead);
         std::unique_ptr<ChunkedReader> s2;
         if (paired) s2.reset(new ChunkedReader({in.f2}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume2));
         ReadSoA c1, c2;
@@ -1454,6 +1609,10 @@ int run(int argc, const char **argv) {
                                  "read %.2f, upload + parse %.2f, host parse %.2f, enqueue %.2f, kernels + format + download %.2f, tuples %.2f, host format %.2f, write %.2f\n",
                          (unsigned long long)tb, (unsigned long long)hb, R.gts.size(), g.read, g.parse, g.hostParse, g.create, g.classify, g.report, g.format, g.write);
         }
+        uint64_t zDev = 0;
+        for (const auto &t : R.gts) zDev += t.zMembers;
+        if (zDev + zHostMembers)
+            std::fprintf(stderr, "Device inflate: %llu BGZF member(s) inflated on the device, %llu on the host\n", (unsigned long long)zDev, (unsigned long long)zHostMembers);
         std::fprintf(stderr, "Stage seconds: index open %.2f, search wall %.2f; %zu GPU thread(s) on %zu device(s): submit (upload + enqueue) %.2f, kernels + download %.2f, results %.2f, tally %.2f; "
                              "output thread: tally %.2f, format %.2f, waiting for the writer %.2f (writer thread: write %.2f); reader thread: assemble %.2f, waiting for the pipeline %.2f\n",
                      R.indexOpenS, secs(ts), R.gts.size(), R.devs.size(), g.create, g.classify, g.results, g.report, R.tm.report, R.tm.format, R.tm.write, R.writeBusy, R.tm.produce, R.tm.wait);

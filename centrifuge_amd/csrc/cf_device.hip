@@ -21,6 +21,7 @@
 #include "cf_kernels.hpp"
 #include "cf_scan.hpp"
 #include "cf_textio.hpp"
+#include "cf_inflate.hpp"
 #include "cf_restore.hpp"
 #include "cf_plan.hpp"
 #include "cf_knobs.hpp"
@@ -276,6 +277,17 @@ __global__ void __launch_bounds__(256) k_compact(DCompact c) {
 __global__ void __launch_bounds__(256) k_text_count(DTextMark m) { text_count_body(m, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(256) k_text_mark(DTextMark m) { text_mark_body(m, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(256) k_text_records(DTextRec d) { text_record_body(d, cf_global_thread()); }
+// BGZF members inflated on the device (cf_inflate.hpp): a wavefront per member, its tables in LDS (4 x 3.9 KiB per block); the
+// one-lane-per-member form — tables in the lane's scratch memory — is kept for the comparison of the two (CF_INFLATE_LANES=1)
+__global__ void __launch_bounds__(256) k_inflate(DInflate d) {
+    __shared__ InfTables tables[256 / CF_WAVE];
+    inflate_body<CF_WAVE>(d, cf_global_thread() / CF_WAVE, cf_lane(), &tables[threadIdx.x / CF_WAVE]);
+}
+__global__ void __launch_bounds__(64) k_inflate_lane(DInflate d) {
+    InfTables tables;
+    inflate_body<1>(d, cf_global_thread(), 0, &tables);
+}
+__global__ void k_text_cut(DTextCut c) { if (cf_global_thread() == 0) text_cut_body(c); }
 __global__ void __launch_bounds__(256) k_text_pack(DTextPack d) { text_pack_body(d, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_size(DTextFmt f) { fmt_size_body(f, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_write(DTextFmt f) { fmt_write_body(f, cf_global_thread()); }
@@ -460,6 +472,16 @@ struct cf_batch {
     PinBuf<uint64_t> hTxTotal;
     PinBuf<uint8_t> hTextOut;
     PinBuf<uint32_t> hTuples;
+    // a BGZF upload (cf_batch_upload_bgzf): the members as the file holds them, their table, what the inflater says; the text
+    // behind the last whole record comes back in hTail
+    DevBuf<uint8_t> zIn;
+    DevBuf<InfMember> zMembers;
+    DevBuf<uint32_t> zErr;
+    DevBuf<InfStatus> zSt;
+    DevBuf<uint64_t> zCut;
+    PinBuf<InfMember> hZMembers;
+    PinBuf<uint64_t> hZCut;                  // the inflater's status, the cut, the markers in front of it
+    PinBuf<uint8_t> hTail;
     bool fromText = false;                   // the resident reads came as text (the plan stage packs them: k_text_pack)
     bool rowsStay = false;                   // cf_batch_wait_text: the rows are formatted on the device, none cross the link
     bool textDone = false;                   // ... and have been (a second wait hands the same text back: the tally is made once)
@@ -2030,6 +2052,109 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
     info->n_reads = nReads; info->n_bases = ts.bases(); info->max_len = ts.maxLen;
 }
 
+// BGZF members (cf_bgzf_reads): the compressed bytes up, inflated on the device into the slot's text buffer behind the head the
+// caller hands in, the text cut behind its last whole record (text_cut_body) and everything in front of the cut parsed by the
+// passes of uploadText; what lies behind the cut goes back to the caller in pinned memory.  Two waits: for the inflater's
+// status and the cut (the record pass is launched with them), and for the parse.
+constexpr uint64_t kBgzfTailRoom = 1u << 20;
+static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf_text_info *info, cf_bgzf_info *zi) {
+    if (in->format != CF_TEXT_FASTA && in->format != CF_TEXT_FASTQ) throw ArgError("cf_bgzf_reads::format is CF_TEXT_FASTA or CF_TEXT_FASTQ");
+    if ((in->n_bytes && !in->members) || (in->head_bytes && !in->head)) throw ArgError("null member / head bytes");
+    if (in->n_bytes >= 0xffff0000ull || in->head_bytes >= 0xffff0000ull) throw ArgError("the text of a batch holds fewer than 2^32 - 65536 bytes (32-bit places in it)");
+    *info = cf_text_info{}; *zi = cf_bgzf_info{};
+    bt->loaded = false; bt->planned = false; bt->running = false; bt->finished = false;
+    // the members' headers (the test BgzfImpl::fill applies, cf_bytesource.cpp) and trailers: where the payloads lie, where their text goes
+    const uint8_t *z = static_cast<const uint8_t *>(in->members);
+    uint64_t nMembers = 0;
+    for (uint64_t at = 0; at < in->n_bytes; nMembers++) {
+        if (in->n_bytes - at < 18) break;
+        at += (uint64_t)(z[at + 16] | (z[at + 17] << 8)) + 1;
+    }
+    bt->hZMembers.ensure(nMembers + 1);
+    uint64_t total = in->head_bytes, at = 0;
+    uint32_t m = 0;
+    for (; at < in->n_bytes; m++) {
+        const uint8_t *h = z + at;
+        bool ok = in->n_bytes - at >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4);
+        const uint64_t xlen = ok ? (uint64_t)(h[10] | (h[11] << 8)) : 0, bsize = ok ? (uint64_t)(h[16] | (h[17] << 8)) + 1 : 0;
+        ok = ok && xlen >= 6 && h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0 && bsize >= 12 + xlen + 8 && bsize <= in->n_bytes - at;
+        uint32_t crc = 0, isize = 0;
+        if (ok) { std::memcpy(&crc, h + bsize - 8, 4); std::memcpy(&isize, h + bsize - 4, 4); ok = isize <= kInfMaxOut; }
+        if (!ok) { zi->corrupt = kInfHeader; zi->bad_member = m; return; }
+        bt->hZMembers.p[m] = InfMember{(uint32_t)(at + 12 + xlen), (uint32_t)(bsize - 12 - xlen - 8), (uint32_t)total, isize, crc};
+        total += isize; at += bsize;
+        if (total >= 0xffff0000ull) throw ArgError("the text of a batch holds fewer than 2^32 - 65536 bytes (32-bit places in it)");
+    }
+    nMembers = m;
+    zi->inflated_bytes = total - in->head_bytes;
+    const bool fasta = in->format == CF_TEXT_FASTA;
+    const uint64_t pieces = (total + kTextPiece - 1) / kTextPiece, recCap = total / 32 + 1024, posCap = fasta ? recCap : 4 * recCap;
+    bt->text.ensure(pieces * kTextPiece + kTextPad);
+    bt->zIn.ensure(in->n_bytes + kInfPad + 8); bt->zMembers.ensure(nMembers + 1); bt->zErr.ensure(nMembers + 1); bt->zSt.ensure(1); bt->zCut.ensure(2);
+    bt->hZCut.ensure(4); bt->hTail.ensure(kBgzfTailRoom + 16);
+    bt->txCnt.ensure(pieces + 32); bt->txBase.ensure(pieces + 32); bt->txPos.ensure(posCap + 32);
+    bt->txTileA.ensure(scan_tiles_for(pieces) + 1); bt->txTileC.ensure(scan_tiles_for(pieces) + 1);
+    bt->rlen.ensure(recCap + 16); bt->seeds.ensure(recCap + 16);
+    bt->txSeqOff.ensure(recCap + 16); bt->txIdOff.ensure(recCap + 16); bt->txIdLen.ensure(recCap + 16);
+    if (!fasta) bt->txQualOff.ensure(recCap + 16);
+    bt->txSt.ensure(1); bt->hTxSt.ensure(1); bt->hTxTotal.ensure(2);
+    HIP_OK(hipMemsetAsync(bt->txSt.p, 0, sizeof(TextStatus), st));
+    HIP_OK(hipMemsetAsync(bt->zSt.p, 0, sizeof(InfStatus), st));
+    uint8_t *text = bt->text.p;
+    HIP_OK(hipMemsetAsync(text + total, 0, pieces * kTextPiece + kTextPad - total, st));
+    if (in->head_bytes) HIP_OK(hipMemcpyAsync(text, in->head, in->head_bytes, hipMemcpyHostToDevice, st));
+    if (nMembers) {
+        HIP_OK(hipMemcpyAsync(bt->zIn.p, in->members, in->n_bytes, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(bt->zMembers.p, bt->hZMembers.p, nMembers * sizeof(InfMember), hipMemcpyHostToDevice, st));
+        const DInflate d{bt->zIn.p, bt->zMembers.p, (uint32_t)nMembers, text, bt->zErr.p, bt->zSt.p, nullptr};
+        static const bool byLane = cfamd::cf_knob("CF_INFLATE_LANES") && std::atoi(cfamd::cf_knob("CF_INFLATE_LANES")) == 1;
+        if (byLane) hipLaunchKernelGGL(k_inflate_lane, dim3((unsigned)((nMembers + 63) / 64)), dim3(64), 0, st, d);
+        else hipLaunchKernelGGL(k_inflate, dim3((unsigned)((nMembers + 256 / CF_WAVE - 1) / (256 / CF_WAVE))), dim3(256), 0, st, d);
+    }
+    const dim3 bl(256);
+    const DTextMark mk{text, total, fasta ? (uint32_t)'>' : (uint32_t)'\n', bt->txCnt.p, bt->txBase.p, bt->txPos.p, posCap};
+    const dim3 gp((unsigned)std::max<uint64_t>(1, (pieces + 255) / 256));
+    if (pieces) hipLaunchKernelGGL(k_text_count, gp, bl, 0, st, mk);
+    scan_enqueue<SCAN_PLAIN>(bt->txCnt.p, pieces, bt->txBase.p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
+    if (pieces) hipLaunchKernelGGL(k_text_mark, gp, bl, 0, st, mk);
+    const DTextCut ct{text, total, bt->txPos.p, bt->txBase.p + pieces, posCap, fasta ? 0u : 1u, in->last ? 1u : 0u, bt->zCut.p};
+    hipLaunchKernelGGL(k_text_cut, dim3(1), dim3(64), 0, st, ct);
+    HIP_OK(hipMemcpyAsync(bt->hZCut.p, bt->zCut.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(bt->hZCut.p + 2, bt->zSt.p, sizeof(InfStatus), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    InfStatus zs; std::memcpy(&zs, bt->hZCut.p + 2, sizeof zs);
+    if (zs.bad) {
+        zi->bad_member = 0xffffffffu - zs.bad;
+        HIP_OK(hipMemcpy(&zi->corrupt, bt->zErr.p + zi->bad_member, 4, hipMemcpyDeviceToHost));
+        if (!zi->corrupt) zi->corrupt = kInfBadCode;
+        return;
+    }
+    const uint64_t cut = bt->hZCut.p[0];
+    if (cut > total) throw std::runtime_error("cf_batch_upload_bgzf: the cut lies behind the text");
+    if (total - cut > kBgzfTailRoom) { info->irregular = kTxTailRoom; return; }
+    if (total > cut) HIP_OK(hipMemcpyAsync(bt->hTail.p, text + cut, total - cut, hipMemcpyDeviceToHost, st));
+    const uint32_t seed0 = (in->global_seed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
+    const DTextRec d{text, cut, bt->txPos.p, bt->zCut.p + 1, posCap, (uint32_t)recCap, (uint32_t)in->format, seed0,
+                     bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, 0u, 1u, 0u, fasta ? nullptr : bt->txQualOff.p};
+    hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap + 255) / 256)), bl, 0, st, d);
+    HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    const TextStatus ts = *bt->hTxSt.p;
+    if (ts.flags) { info->irregular = ts.flags; return; }
+    uint64_t nq = fasta ? bt->hZCut.p[1] : bt->hZCut.p[1] >> 2;
+    if (in->max_reads && nq > in->max_reads) nq = in->max_reads;
+    sizeBatch(bt, nq, ts.words(), ts.bases(), ts.maxLen, false);
+    bindBatch(bt);
+    HIP_OK(hipEventRecord(bt->ev[8], st));
+    bt->fromText = true; bt->fromBytes = false; bt->densePending = 0; bt->revMade = false; bt->nmaskZeroOf = nullptr;
+    bt->textFastq = !fasta;
+    bt->loaded = true;
+    info->n_reads = nq; info->n_bases = ts.bases(); info->max_len = ts.maxLen;
+    zi->tail = reinterpret_cast<const char *>(bt->hTail.p); zi->tail_bytes = total - cut;
+}
+
 // ======================================================================= batch C ABI
 cf_status cf_host_alloc(void **p, size_t bytes) {
     if (!p) return CF_ERR_ARG;
@@ -2233,6 +2358,15 @@ cf_status cf_batch_upload_text(cf_batch *bt, const cf_text_reads *in, void *stre
         HIP_OK(hipSetDevice(bt->cl->ix->device));
         if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
         uploadText(bt, in, static_cast<hipStream_t>(streamv), info);
+    });
+}
+
+cf_status cf_batch_upload_bgzf(cf_batch *bt, const cf_bgzf_reads *in, void *streamv, cf_text_info *info, cf_bgzf_info *zi) {
+    if (!bt || !in || !info || !zi) return CF_ERR_ARG;
+    return guard([&] {
+        HIP_OK(hipSetDevice(bt->cl->ix->device));
+        if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
+        uploadBgzf(bt, in, static_cast<hipStream_t>(streamv), info, zi);
     });
 }
 

@@ -544,9 +544,9 @@ void parseFastqChunk(const char *p, const char *e, bool firstOfFile, int trim5, 
 }
 
 // ----------------------------------------------------------------------------------------
-ChunkedReader::ChunkedReader(std::vector<std::string> files, ReadFormat fmt, int trim5, int trim3, uint32_t globalSeed, int threads, bool pack, uint64_t startOffset)
+ChunkedReader::ChunkedReader(std::vector<std::string> files, ReadFormat fmt, int trim5, int trim3, uint32_t globalSeed, int threads, bool pack, uint64_t startOffset, std::string startHead)
     : files_(std::move(files)), fmt_(fmt), trim5_(trim5), trim3_(trim3), globalSeed_(globalSeed),
-      parallel_(fmt == ReadFormat::Fasta || fmt == ReadFormat::Fastq), pack_(pack), startOffset_(startOffset) {
+      parallel_(fmt == ReadFormat::Fasta || fmt == ReadFormat::Fastq), pack_(pack), startOffset_(startOffset), startHead_(std::move(startHead)) {
     if (!parallel_) { seqSrc_.reset(new ReadSource(files_, fmt_, trim5_, trim3_)); return; }
     const int n = std::max(1, threads);
     maxInFlight_ = (size_t)n * 2 + 2;
@@ -699,7 +699,7 @@ void ChunkedReader::ioLoop() {
     const size_t kBlock = cfamd::cf_knob("CF_INGEST_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_INGEST_BLOCK"), nullptr, 10)) : (size_t)(32u << 20);
     try {
         for (const std::string &path : files_) {
-            ByteSource src(path, (int)std::max<size_t>(1, parsers_.size()));      // plain / stdin / gzip (in-process) / bzip2; throws when it cannot be opened
+            ByteSource src(path, (int)std::max<size_t>(1, parsers_.size()), startOffset_);      // plain / stdin / gzip (in-process) / bzip2; throws when it cannot be opened
             int fd = -1; uint64_t fsize = 0;
             if ((!cfamd::cf_knob("CF_INGEST_STREAM") || startOffset_) && src.regularFile(fd, fsize)) {
                 // A plain file is dealt out as RANGES: this thread only finds where records start (a look at the last
@@ -732,9 +732,10 @@ void ChunkedReader::ioLoop() {
             }
             // The file is read straight into the block a parser will get (one copy: the read itself); what follows the
             // last whole record is carried over to the front of the next block.
-            std::vector<char> carry;
+            std::vector<char> carry(startHead_.begin(), startHead_.end());     // (a BGZF file taken over in mid-file: the text in front of the member)
             CharBuf buf;
-            bool first = true, eof = false;
+            bool first = startOffset_ == 0, eof = false;
+            startOffset_ = 0; startHead_.clear();            // (the first file only)
             while (!eof) {
                 if (!buf.p) {
                     { std::lock_guard<std::mutex> lk(mu_); if (!rawPool_.empty()) { buf = std::move(rawPool_.back()); rawPool_.pop_back(); } }

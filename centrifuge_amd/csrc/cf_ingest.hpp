@@ -91,8 +91,11 @@ struct ReadSoA {
 class ChunkedReader {
 public:
     // pack: the parser threads also make every chunk's packed form (ReadSoA::pk)
-    // startOffset: where in the (first, plain) file to begin — a record start (a run that changes over from the device text path)
-    ChunkedReader(std::vector<std::string> files, ReadFormat fmt, int trim5, int trim3, uint32_t globalSeed, int threads, bool pack = false, uint64_t startOffset = 0);
+    // startOffset: where in the (first, plain) file to begin — a record start (a run that changes over from the device text path).
+    // For a BGZF file it is the byte a member starts at, and startHead the text in front of that member's: from a record start to
+    // the member's first byte (what cf_batch_upload_bgzf handed back as the tail of the members before it).
+    ChunkedReader(std::vector<std::string> files, ReadFormat fmt, int trim5, int trim3, uint32_t globalSeed, int threads, bool pack = false, uint64_t startOffset = 0,
+                  std::string startHead = std::string());
     ~ChunkedReader();
     // Next chunk of parsed reads in input order; false at the end.  Reads whose name was empty
     // come back with an empty name (the caller substitutes the read's ordinal, pat.cpp:838-842).
@@ -124,6 +127,7 @@ private:
     bool parallel_;
     bool pack_ = false;
     uint64_t startOffset_ = 0;
+    std::string startHead_;
     std::unique_ptr<ReadSource> seqSrc_;     // raw / command-line formats: sequential path
 
     // Buffers go round: a parsed chunk handed out by next() leaves the caller's previous arrays behind, the parser threads

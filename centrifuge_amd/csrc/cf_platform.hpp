@@ -53,6 +53,7 @@ inline uint32_t cf_swap1(uint32_t v) { return emu_wave_lane() < 0 ? v : (uint32_
 #else
 inline uint32_t cf_swap1(uint32_t v) { return v; }          // never reached with one-lane chains
 #endif
+inline void cf_wave_fence() { cf_compiler_fence(); }
 inline int cf_popc32(uint32_t x) { return __builtin_popcount(x); }
 inline uint32_t cf_brev32(uint32_t x) { uint32_t r = 0; for (int i = 0; i < 32; i++) { r = (r << 1) | (x & 1u); x >>= 1; } return r; }
 inline uint64_t cf_brev64(uint64_t x) { uint64_t r = 0; for (int i = 0; i < 64; i++) { r = (r << 1) | (x & 1ull); x >>= 1; } return r; }
@@ -97,6 +98,9 @@ CF_DEV int cf_ctz64(uint64_t x) { return __builtin_ctzll(x); }
 // keeps the compiler from moving memory accesses across it (LDS ops of one wavefront retire in order,
 // so this is all a same-wave LDS write -> read hand-off between lanes needs)
 CF_DEV void cf_compiler_fence() { asm volatile("" ::: "memory"); }
+// the same for GLOBAL memory: what the wavefront's lanes stored before it is what any of its lanes loads behind it (a fence of
+// wavefront scope: the memory operations of one wavefront are carried out in order, so it costs no instruction)
+CF_DEV void cf_wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
 // value of the neighbouring lane (lane ^ 1): one DPP move (quad_perm [1,0,3,2]), no LDS crossbar
 CF_DEV uint32_t cf_swap1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false); }
 CF_DEV int cf_popc32(uint32_t x) { return __popc(x); }

@@ -28,7 +28,8 @@ enum : uint32_t { kTextFasta = 0, kTextFastq = 1 };
 enum : uint32_t {
     kTxBadStart = 1u, kTxNoNameEnd = 2u, kTxEmptyName = 4u, kTxCarriageReturn = 8u, kTxBadBase = 16u, kTxEmptySeq = 32u,
     kTxBadPlus = 64u, kTxQualLen = 128u, kTxBadQual = 256u, kTxLineCount = 512u, kTxTooMany = 1024u,
-    kTxMateCount = 2048u                                 // (made by the host: the two blocks of a paired upload hold different numbers of records)
+    kTxMateCount = 2048u,                                // (made by the host: the two blocks of a paired upload hold different numbers of records)
+    kTxTailRoom = 4096u                                  // (made by the host: a BGZF upload leaves more text behind its last whole record than the slot keeps room for)
 };
 
 constexpr uint32_t kTextStripes = 64;                   // the block's sums are kept in that many places (a wavefront adds to one of them:

@@ -313,6 +313,34 @@ typedef struct {
     uint32_t irregular;        /* 0 = the slot holds the block's reads; else why the block is not in the plain form (a bit set) */
 } cf_text_info;
 cf_status cf_batch_upload_text(cf_batch *, const cf_text_reads *, void *hip_stream, cf_text_info *info);
+/* BGZF members in (bgzip, htslib: a gzip file of independent members of at most 64 KiB that carry their own compressed size in a
+ * 'BC' extra field): the COMPRESSED bytes cross the link and are inflated on the device (one wavefront per member), the text
+ * stays there for the passes of cf_batch_upload_text.  The text of a call is  head + inflate(members);  it starts at a record
+ * start — by induction from the file's start, where head is empty — and is CUT behind its last whole record by a purely
+ * syntactic rule:
+ *   FASTQ  the cut is behind the last '\n' whose count from the text's start is a multiple of 4
+ *   FASTA  the cut is in front of the last '>' that starts the text or follows a '\n'
+ *   last   (no member follows) the cut is the text's end; a FASTQ text that then does not end a record is `irregular`
+ * What lies in front of the cut is parsed exactly as a block of cf_batch_upload_text is (same plain form, same `irregular` bits,
+ * cf_batch_wait_text and cf_batch_set_text_columns work on the batch); what lies behind it comes back as `tail`, to be handed in
+ * as the next call's head.  A text without a whole record is legal: n_reads == 0, everything is tail.  The call waits for the
+ * inflater and the parse.  The slot holds NO batch when
+ *   - the tail is larger than the room the slot keeps for it (1 MiB): info->irregular has CF_TEXT_TAIL_ROOM set
+ *   - head_bytes + the members' ISIZE sum reaches 2^32 - 65536 (known before anything is uploaded): CF_ERR_ARG
+ *   - a member is corrupt: zinfo->corrupt != 0 says why (a malformed deflate stream, text that is not ISIZE bytes, a CRC32 that is
+ *     not the trailer's — the checks of the host reader —, or a header that is not BGZF's), zinfo->bad_member is the first one's index */
+#define CF_TEXT_TAIL_ROOM 4096u
+typedef struct {
+    const void *members;  uint64_t n_bytes;     /* whole BGZF members, as the file holds them */
+    const char *head;     uint64_t head_bytes;  /* text that precedes them: the previous call's tail (NULL/0 at a file's start) */
+    int32_t  format;      uint32_t global_seed; uint64_t max_reads;
+    int32_t  last;        /* no member follows: the text's end is a record's end */
+} cf_bgzf_reads;
+typedef struct {
+    const char *tail; uint64_t tail_bytes;      /* text behind the last whole record, in the slot's pinned memory, valid until its next upload */
+    uint64_t inflated_bytes; uint32_t corrupt;  uint32_t bad_member;
+} cf_bgzf_info;
+cf_status cf_batch_upload_bgzf(cf_batch *, const cf_bgzf_reads *, void *hip_stream, cf_text_info *, cf_bgzf_info *);
 /* Out: the batch's rows as text — by default the columns centrifuge prints by default, readID seqID taxID score 2ndBestScore
  * hitLength queryLength numMatches; any other list after cf_batch_set_text_columns —, one line per row, query order, formatted on the device from the rows the kernels left there (no row crosses the
  * link) with the readIDs copied out of the uploaded block; in the slot's pinned memory, valid until its next upload.  Needs the
