@@ -157,7 +157,7 @@ EXPORTS = [
     "cf_batch_max_scores", "cf_report_create", "cf_report_destroy", "cf_report_add", "cf_report_add_narrow", "cf_report_add_counts", "cf_report_reset_counts", "cf_report_write", "cf_report_serialize", "cf_report_merge",
     "cf_index_text_verify_rate", "cf_index_text_verify_build_ms", "cf_index_wide_ftab_chars", "cf_index_occ_planes", "cf_index_occ_planes_build_ms", "cf_index_resolve_rate", "cf_index_resolve_build_ms", "cf_index_walk_bound", "cf_index_resolve_by_position", "cf_slot_estimate_bytes", "cf_batch_reclassify_async", "cf_comm_init_all", "cf_comm_destroy", "cf_counts_allreduce_group", "cf_stream_create", "cf_stream_destroy", "cf_device_count", "cf_device_numa_node", "cf_thread_bind_near_device",
     "cf_report_adopt_counts", "cf_debug_scan", "cf_host_alloc", "cf_host_free", "cf_batch_alloc", "cf_batch_upload_packed_async", "cf_classify_async", "cf_batch_download_async",
-    "cf_batch_submit", "cf_batch_wait", "cf_batch_upload", "cf_batch_set_limits", "cf_batch_upload_bgzf",
+    "cf_batch_submit", "cf_batch_wait", "cf_batch_upload", "cf_batch_set_limits", "cf_batch_upload_bgzf", "cf_batch_upload_bgzf_pair",
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
 ]
@@ -228,6 +228,7 @@ def lib():
         "cf_batch_upload": (i32, [vp, vp, vp, vp, u64, i32, vp]),
         "cf_batch_upload_text": (i32, [vp, C.POINTER(TextReads), vp, C.POINTER(TextInfo)]),
         "cf_batch_upload_bgzf": (i32, [vp, C.POINTER(BgzfReads), vp, C.POINTER(TextInfo), C.POINTER(BgzfInfo)]),
+        "cf_batch_upload_bgzf_pair": (i32, [vp, C.POINTER(BgzfReads), C.POINTER(BgzfReads), vp, C.POINTER(TextInfo), C.POINTER(BgzfInfo), C.POINTER(BgzfInfo)]),
         "cf_batch_wait_text": (i32, [vp, C.POINTER(ResultsText)]),
         "cf_text_column_of": (C.c_int32, [cp]), "cf_batch_set_text_columns": (i32, [vp, vp, u32]),
         "cf_counts_get_single": (i32, [vp, vp]),
@@ -640,6 +641,29 @@ class Slot:
         tail = C.string_at(zinfo.tail, zinfo.tail_bytes) if zinfo.tail_bytes else b""
         _check(self.L.cf_classify_async(self.clf.h, self.h, stream))
         return tail, info, zinfo
+
+    def submit_bgzf_pair(self, members1, members2, fmt, head1=b"", head2=b"", last1=False, last2=False, max_reads=0, seed=0, stream=None, fmt2=None):
+        """whole BGZF members of the two mate files (cf_batch_upload_bgzf_pair: inflated, cut behind a common record and parsed on the
+        device; head1 / head2 = the tails the call before returned; max_reads counts pairs), then the kernels.
+        -> tail1, tail2, TextInfo, BgzfInfo of file 1, of file 2; info.irregular != 0 or a zinfo.corrupt != 0: nothing was
+        submitted (the tails are None).  (fmt2: a format of its own for the second mate — the ABI refuses one that differs)"""
+        keep, brs = [], []
+        for members, head, last, f in ((members1, head1, last1, fmt), (members2, head2, last2, fmt if fmt2 is None else fmt2)):
+            buf = np.frombuffer(members, dtype=np.uint8) if len(members) else np.zeros(1, dtype=np.uint8)
+            hbuf = np.frombuffer(head, dtype=np.uint8) if len(head) else np.zeros(1, dtype=np.uint8)
+            br = BgzfReads()
+            br.members, br.n_bytes, br.head, br.head_bytes = buf.ctypes.data, len(members), hbuf.ctypes.data, len(head)
+            br.format, br.global_seed, br.max_reads, br.last = int(f), int(seed), int(max_reads), int(bool(last))
+            keep += [buf, hbuf, br]
+            brs.append(br)
+        info, z1, z2 = TextInfo(), BgzfInfo(), BgzfInfo()
+        self._keep = tuple(keep)
+        _check(self.L.cf_batch_upload_bgzf_pair(self.h, C.byref(brs[0]), C.byref(brs[1]), stream, C.byref(info), C.byref(z1), C.byref(z2)))
+        if info.irregular or z1.corrupt or z2.corrupt:
+            return None, None, info, z1, z2
+        tails = [C.string_at(z.tail, z.tail_bytes) if z.tail_bytes else b"" for z in (z1, z2)]
+        _check(self.L.cf_classify_async(self.clf.h, self.h, stream))
+        return tails[0], tails[1], info, z1, z2
 
     def set_text_columns(self, cols):
         """the columns later wait_text() calls print: names (as --tab-fmt-cols spells them) or COL_* codes; [] = the default eight"""

@@ -9,6 +9,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <zlib.h>
 #include <cerrno>
 #include <atomic>
 
@@ -52,6 +53,7 @@ struct Opts {
     int gpus = 1;                                       // --gpus N | all: devices device .. device+N-1, the index replicated on each
     int slots = 2;                                      // --slots: GPU threads (batch slots, each with its stream) per device
     bool slotsSet = false;
+    int devInflate = 1;                                 // --device-inflate off | unpaired | all: which BGZF inputs are inflated on the device (0, 1, 2)
     bool hostIo = false;                                // --host-io: the parser pool and the formatter threads for every input (no device text path)
     int smallRangeRows = 0;                             // --small-range-rows: cf_index_options::small_range_rows (0 = automatic, -1 = off)
     double hbmBudgetGb = 0;                             // --hbm-budget-gb: cf_index_options::hbm_budget_bytes (0 = what the device has free)
@@ -93,8 +95,11 @@ void usage(std::FILE *f) {
         "          --host-io (reads are parsed and rows printed by host threads for every input; default: plain FASTA / FASTQ files go up as\n"
         "          text and the rows come back as text, formatted on the device — the default columns, any --tab-fmt-cols list of up\n"
         "          to 32 columns, --out-fmt sam — same bytes either way; an unpaired BGZF .gz file (bgzip, htslib) goes up compressed and\n"
-        "          is inflated on the device, the parser pool taking the file over at its first record outside the plain form; mates,\n"
+        "          is inflated on the device, the parser pool taking the file over at its first record outside the plain form; BGZF mates,\n"
         "          other .gz files, .bz2, stdin, -s and -5/-3 keep the host threads)\n"
+        "          --device-inflate <off|unpaired|all> (which BGZF inputs are inflated on the device: none, an unpaired file (default),\n"
+        "          or also a -1/-2 pair of BGZF files — both texts are cut behind a common record on the device —, the parser pool\n"
+        "          taking both files over at the first run the device refuses)\n"
         " Index:   --hbm-budget-gb <float> (device memory the index may take, files + derived tables; default: what is free less a\n"
         "          reserve for the batch slots)  --small-range-rows <-1|0|2..15> (search ranges of up to that many rows are finished\n"
         "          against the text; 0 = decided from how repeat-rich the indexed collection is, -1 = off; results do not depend on it)\n"
@@ -181,6 +186,11 @@ Opts parse(int argc, const char **argv) {
         else if (a == "--gpu-list") { for (auto &x : splitComma(val())) o.gpuList.push_back(std::atoi(x.c_str())); }
         else if (a == "--slots") { o.slots = std::atoi(val().c_str()); o.slotsSet = true; if (o.slots < 1) die("--slots arg must be at least 1"); }
         else if (a == "--host-io") o.hostIo = true;
+        else if (a == "--device-inflate") {
+            const std::string m = val();
+            if (m == "off") o.devInflate = 0; else if (m == "unpaired") o.devInflate = 1; else if (m == "all") o.devInflate = 2;
+            else die("--device-inflate arg must be off, unpaired or all");
+        }
         else if (a == "--small-range-rows") { o.smallRangeRows = std::atoi(val().c_str()); if (o.smallRangeRows < -1 || o.smallRangeRows == 1 || o.smallRangeRows > 15) die("--small-range-rows arg must be -1 (off), 0 (automatic) or 2 .. 15"); }
         else if (a == "--expected-reads") { o.expectedReads = std::atoll(val().c_str()); if (o.expectedReads < 0) die("--expected-reads arg must not be negative"); }
         else if (a == "--hbm-budget-gb") { o.hbmBudgetGb = std::atof(val().c_str()); if (o.hbmBudgetGb < 0) die("--hbm-budget-gb arg must not be negative"); }
@@ -224,6 +234,41 @@ std::string findIndex(const std::string &base) {                            // a
     die("Could not locate a Centrifuge index corresponding to basename \"" + base + "\"");
 }
 
+// a BGZF member at byte `at` of a mapped file: its size in the file and the size of its text; false: not a BGZF member (or one cut short)
+bool bgzfMemberAt(const unsigned char *z, uint64_t fsize, uint64_t at, uint64_t &bsize, uint64_t &isize) {
+    if (fsize - at < 18) return false;
+    const unsigned char *h = z + at;
+    const uint64_t xlen = (uint64_t)(h[10] | (h[11] << 8));
+    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || xlen < 6 || h[12] != 'B' || h[13] != 'C' || h[14] != 2 || h[15] != 0) return false;
+    bsize = (uint64_t)(h[16] | (h[17] << 8)) + 1;
+    if (bsize < 12 + xlen + 8 || bsize > fsize - at) return false;
+    uint32_t v; std::memcpy(&v, h + bsize - 4, 4);
+    isize = v;
+    return isize <= 65536;
+}
+
+// bytes of text per record at the start of a BGZF file: its first members (256 KiB of text at most) inflated here, on the host, and
+// their records counted as the device counts them; 0: not to be had
+double bgzfSampleRecordBytes(const unsigned char *z, uint64_t fsize, bool fasta) {
+    uint64_t at = 0, bs = 0, is = 0, bytes = 0, marks = 0;
+    std::vector<unsigned char> text(65536);
+    unsigned char prev = '\n';
+    while (at < fsize && bytes < (256u << 10) && bgzfMemberAt(z, fsize, at, bs, is)) {
+        const uint64_t xlen = (uint64_t)(z[at + 10] | (z[at + 11] << 8));
+        z_stream zs{};
+        if (inflateInit2(&zs, -15) != Z_OK) return 0;
+        zs.next_in = const_cast<Bytef *>(z + at + 12 + xlen); zs.avail_in = (uInt)(bs - 12 - xlen - 8);
+        zs.next_out = text.data(); zs.avail_out = (uInt)is;
+        const int rc = inflate(&zs, Z_FINISH);
+        inflateEnd(&zs);
+        if (rc != Z_STREAM_END || zs.avail_out) return 0;
+        for (uint64_t i = 0; i < is; i++) { marks += fasta ? (text[i] == '>' && prev == '\n') : text[i] == '\n'; prev = text[i]; }
+        bytes += is; at += bs;
+    }
+    const double rec = fasta ? (double)marks : (double)marks / 4;
+    return rec >= 1 ? (double)bytes / rec : 0;
+}
+
 #define CF_TRY(expr)                                                                                        \
     do {                                                                                                    \
         cf_status s_ = (expr);                                                                              \
@@ -261,6 +306,10 @@ struct Batch {
     // ... or a run of whole BGZF members of a .gz file (tOff, tLen: the compressed bytes) that are inflated on the device (classifyBgzf)
     bool tBgzf = false;
     uint64_t tMembers = 0;
+    // ... or of the two BGZF files of mates (tFd2 >= 0; classifyBgzfPair): either file's range may be empty, tLast2 is the second
+    // file's end, tCum / tCum2 the text (ISIZE sums) of either file up to the run's end
+    bool tLast2 = false;
+    uint64_t tCum = 0, tCum2 = 0;
 };
 
 // Numbers handed in by position (the blocks of an input in file order), each caller learning the sum of all earlier positions:
@@ -349,6 +398,7 @@ struct GpuThread {
     uint64_t textBlocks = 0, hostBlocks = 0;        // blocks that went up as text / were parsed on the host (not in the plain form)
     uint64_t zMembers = 0;                          // BGZF members this thread had inflated on the device
     std::string zHead;                              // the text in front of the run in hand (the tail of the run before it)
+    std::string zHead2;                             // ... of the second file of mates
 };
 
 struct Runner {
@@ -389,6 +439,9 @@ struct Runner {
     bool zStopped = false;                          // a run was refused: the runs behind it do nothing
     uint64_t zResumeOff = 0;                        // ... the byte of the file its first member starts at
     std::string zResumeHead, zWhy;                  // ... the text in front of that member, and what the device said
+    std::string zTail2, zResumeHead2;               // mates: the same for the second file
+    uint64_t zResumeOff2 = 0;
+    uint64_t zCons = 0, zCons2 = 0;                 // mates: the text of either file that whole pairs have used up so far (their ratio steers the producer)
 
     ~Runner() {                                     // error paths leave through here as well
         try { waitWrite(); } catch (...) {}          // (a run that ends on an error: the writer must be done with the file before it is closed)
@@ -886,6 +939,85 @@ struct Runner {
         b.nq = 0;
     }
 
+    // A run of whole BGZF members of the two files of mates on one GPU thread: classifyBgzf for two files.  Both byte ranges go into
+    // the thread's pinned buffer and up as they are (cf_batch_upload_bgzf_pair: inflated by one launch, both texts cut behind the same
+    // number of whole records) with the two tails of the run before in front; both tails that come back are handed on at once.
+    // readChain counts pairs.  A run the device refuses ends the way for both files.
+    void classifyBgzfPair(Batch &b, GpuThread &g) {
+        auto t0 = std::chrono::steady_clock::now();
+        auto lap = [&](double &acc) { const auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(t - t0).count(); t0 = t; };
+        const uint64_t at2 = (b.tLen + 4095) & ~4095ull, need = at2 + b.tLen2;
+        if (need + 64 > g.tinCap) {
+            if (g.tin) cf_host_free(g.tin);
+            g.tin = nullptr; g.tinCap = 0;
+            void *q = nullptr;
+            const size_t want = (size_t)(need + need / 8 + 4096);
+            CF_TRY(cf_host_alloc(&q, want));
+            g.tin = static_cast<char *>(q); g.tinCap = want;
+        }
+        if (b.tLen) readFileRange(b.tFd, g.tin, (size_t)b.tLen, b.tOff, *b.tPath);
+        if (b.tLen2) readFileRange(b.tFd2, g.tin + at2, (size_t)b.tLen2, b.tOff2, *b.tPath2);
+        lap(g.tm.read);
+        CF_TRY(cf_batch_set_result_format(g.slot, CF_RESULTS_NARROW));
+        cf_bgzf_reads in1{}, in2{};
+        in1.members = g.tin; in1.n_bytes = b.tLen; in1.format = o.format == ReadFormat::Fasta ? CF_TEXT_FASTA : CF_TEXT_FASTQ;
+        in1.global_seed = o.seed; in1.max_reads = 0; in1.last = b.tLast ? 1 : 0;
+        in2 = in1;
+        in2.members = g.tin + at2; in2.n_bytes = b.tLen2; in2.last = b.tLast2 ? 1 : 0;
+        cf_text_info info{};
+        cf_bgzf_info z1{}, z2{};
+        (void)tailChain.enter(b.tIdx);
+        bool skip = zStopped;
+        if (!skip) {
+            g.zHead = zTail; g.zHead2 = zTail2;
+            in1.head = g.zHead.data(); in1.head_bytes = g.zHead.size();
+            in2.head = g.zHead2.data(); in2.head_bytes = g.zHead2.size();
+            const cf_status st = cf_batch_upload_bgzf_pair(g.slot, &in1, &in2, g.stream, &info, &z1, &z2);
+            // (texts beyond the batch's 32-bit places are refused before anything is uploaded: the host path has no such limit)
+            if (st != CF_OK && st != CF_ERR_ARG) { tailChain.fail(); die(std::string("centrifuge-class: ") + cf_strerror(st) + ": " + cf_last_error()); }
+            if (st != CF_OK || info.irregular || z1.corrupt || z2.corrupt) {
+                zStopped = true; zResumeOff = b.tOff; zResumeOff2 = b.tOff2; zResumeHead = g.zHead; zResumeHead2 = g.zHead2;
+                zWhy = (z1.corrupt || z2.corrupt) ? "a corrupt member" : st != CF_OK ? "a run beyond the batch's size" : "a record outside the plain form";
+                skip = true;
+            } else {
+                zTail.assign(z1.tail, (size_t)z1.tail_bytes); zTail2.assign(z2.tail, (size_t)z2.tail_bytes);
+                std::lock_guard<std::mutex> lk(tailChain.mu);            // (the producer reads the two together)
+                zCons = b.tCum - z1.tail_bytes; zCons2 = b.tCum2 - z2.tail_bytes;
+            }
+        }
+        tailChain.leave(0);
+        lap(g.tm.parse);
+        const uint64_t nPairs = skip ? 0 : info.n_reads / 2;
+        const uint64_t base = readChain.enter(b.tIdx);
+        readChain.leave(nPairs);
+        const uint64_t take = base >= o.upto ? 0 : std::min<uint64_t>(nPairs, o.upto - base);
+        if (!skip && base + nPairs >= o.upto) uptoReached = true;
+        const char *text = "";
+        uint64_t nText = 0;
+        if (take) {
+            if (take < nPairs) {                                        // the run -u ends in: once more, its first pairs only
+                in1.max_reads = in2.max_reads = take;
+                CF_TRY(cf_batch_upload_bgzf_pair(g.slot, &in1, &in2, g.stream, &info, &z1, &z2));
+                if (info.irregular || z1.corrupt || z2.corrupt || info.n_reads != 2 * take) die("internal error: a run of members changed between two uploads");
+            }
+            CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
+            lap(g.tm.create);
+            cf_results_text res{};
+            CF_TRY(cf_batch_wait_text(g.slot, &res));
+            lap(g.tm.classify);
+            if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
+            text = res.text; nText = res.n_bytes;
+            textBatches++; g.textBlocks++;
+            lap(g.tm.report);
+        }
+        if (!skip) g.zMembers += b.tMembers;
+        const uint64_t at = outChain.enter(b.tIdx);
+        if (outRegular) { outChain.leave(nText); if (nText) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
+        else { try { if (nText) writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
+        lap(g.tm.write);
+        b.nq = 0;
+    }
+
     // the report file with its stderr lines (centrifuge.cpp:3134-3141,3231-3319; aln_sink.h:471-472)
     template <typename Hms>
     void writeReport(cf_report *r, const std::string &path, const Hms &hms) {
@@ -1199,7 +1331,7 @@ int run(int argc, const char **argv) {
                     queue.pop_front();
                 }
                 cv.notify_all();
-                if (b->endOfInput < 0) { if (b->isText && b->tBgzf) R.classifyBgzf(*b, g); else if (b->isText) R.classifyText(*b, g, wi); else R.classify(*b, g); }
+                if (b->endOfInput < 0) { if (b->isText && b->tBgzf && b->tFd2 >= 0) R.classifyBgzfPair(*b, g); else if (b->isText && b->tBgzf) R.classifyBgzf(*b, g); else if (b->isText) R.classifyText(*b, g, wi); else R.classify(*b, g); }
                 {
                     std::lock_guard<std::mutex> lk(mu);
                     const uint64_t sq = b->seq;
@@ -1265,7 +1397,7 @@ int run(int argc, const char **argv) {
         const bool paired = in.paired;
         struct stat isb;
         uint64_t resume1 = 0, resume2 = 0, resumeId = 0;              // where the parser pool takes over from the text path (mates, BGZF files)
-        std::string resumeHead;                                       // ... a BGZF file: the text in front of the member at resume1
+        std::string resumeHead, resumeHead2;                          // ... a BGZF file: the text in front of the member at resume1 (resume2)
         if (R.textCapable && paired && !o.dumpReads && in.f1 != "-" && in.f2 != "-" && ::stat(in.f1.c_str(), &isb) == 0 && S_ISREG(isb.st_mode) &&
             ::stat(in.f2.c_str(), &isb) == 0 && S_ISREG(isb.st_mode)) {
             // Mates on the device text path: the first file is cut like an unpaired one; the second where it holds as many records
@@ -1343,6 +1475,85 @@ int run(int argc, const char **argv) {
                 if (!changeOver || R.uptoReached) continue;
                 resume1 = pos1; resume2 = pos2; resumeId = pairs;     // the parser pool goes on from here
             }
+            int zfd1 = -1, zfd2 = -1; uint64_t zs1 = 0, zs2 = 0;
+            const bool devInflateAll = o.devInflate == 2 && !(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE")));
+            if (devInflateAll && src1.bgzfFile(zfd1, zs1) && src2.bgzfFile(zfd2, zs2) && zs1 && zs2) {
+                // Two BGZF files of mates (--device-inflate all): the members of both are hopped here by their headers and dealt out
+                // as runs — some whole members of the first file and some of the second, CF_TEXT_BLOCK bytes of compressed plus
+                // inflated size together at most; the device cuts both texts of a run behind a common record and hands back two
+                // tails.  Which file the run's next member comes from keeps the second file's text so far (the ISIZE sums: no
+                // member is inflated for it) at rho times the first file's, rho being the text either file spends on a record:
+                // sampled from the files' first members at first, then what whole pairs have in fact used up — so the tails stay
+                // a member's size whatever the two files' records look like.  The first runs are small: a poor sample costs little.
+                if (!drain()) { aborted = true; break; }
+                R.waitWrite();
+                std::fflush(R.out);
+                R.outFd = fileno(R.out);
+                struct stat sb;
+                R.outRegular = ::fstat(R.outFd, &sb) == 0 && S_ISREG(sb.st_mode);
+                R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
+                R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
+                R.outMap = false;
+                R.readChain.reset(); R.outChain.reset(); R.tailChain.reset(); R.uptoReached = false;
+                R.zTail.clear(); R.zTail2.clear(); R.zStopped = false; R.zResumeHead.clear(); R.zResumeHead2.clear(); R.zWhy.clear(); R.zCons = R.zCons2 = 0;
+                const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
+                void *zm1 = ::mmap(nullptr, (size_t)zs1, PROT_READ, MAP_SHARED, zfd1, 0);
+                if (zm1 == MAP_FAILED) die("Error: could not map \"" + in.f1 + "\"");
+                void *zm2 = ::mmap(nullptr, (size_t)zs2, PROT_READ, MAP_SHARED, zfd2, 0);
+                if (zm2 == MAP_FAILED) { ::munmap(zm1, (size_t)zs1); die("Error: could not map \"" + in.f2 + "\""); }
+                struct Unmap { void *a, *b; size_t na, nb; ~Unmap() { ::munmap(a, na); ::munmap(b, nb); } } unmap{zm1, zm2, (size_t)zs1, (size_t)zs2};
+                const unsigned char *zp[2] = {static_cast<const unsigned char *>(zm1), static_cast<const unsigned char *>(zm2)};
+                const uint64_t zsz[2] = {zs1, zs2};
+                const bool fasta = o.format == ReadFormat::Fasta;
+                const double rb1 = bgzfSampleRecordBytes(zp[0], zs1, fasta), rb2 = bgzfSampleRecordBytes(zp[1], zs2, fasta);
+                double rho = rb1 > 0 && rb2 > 0 ? rb2 / rb1 : 1.0;
+                uint64_t pos[2] = {0, 0}, cum[2] = {0, 0}, idx = 0;
+                size_t budget = std::min<size_t>(kBlock, (size_t)1 << 20);
+                bool badHeader = false;
+                while ((pos[0] < zs1 || pos[1] < zs2) && !R.uptoReached && !badHeader) {
+                    const auto tp0 = std::chrono::steady_clock::now();
+                    {   // what the pairs so far have used up of either file
+                        std::lock_guard<std::mutex> lk(R.tailChain.mu);
+                        if (R.zCons && R.zCons2) rho = (double)R.zCons2 / (double)R.zCons;
+                    }
+                    uint64_t end[2] = {pos[0], pos[1]}, bytes = 0, nMem = 0, bs = 0, is = 0;
+                    for (;;) {
+                        // the file that is behind its share gives the next member (the one that is left, when the other has run out)
+                        int f = (double)cum[1] >= rho * (double)cum[0] ? 0 : 1;
+                        if (end[f] >= zsz[f]) f ^= 1;
+                        if (end[f] >= zsz[f]) break;
+                        if (!bgzfMemberAt(zp[f], zsz[f], end[f], bs, is)) { badHeader = true; break; }
+                        if (nMem && bytes + bs + is > budget) break;
+                        bytes += bs + is; end[f] += bs; cum[f] += is; nMem++;
+                    }
+                    if (!nMem) break;
+                    budget = std::min<size_t>(kBlock, budget * 2);
+                    std::unique_ptr<Batch> b;
+                    { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
+                    if (!b) b = std::make_unique<Batch>();
+                    b->nq = 0; b->endOfInput = -1; b->paired = true; b->narrowRows = false;
+                    b->isText = true; b->tBgzf = true; b->tMembers = nMem; b->tIdx = idx++; b->tFirst = pos[0] == 0 && pos[1] == 0;
+                    b->tFd = zfd1; b->tOff = pos[0]; b->tLen = end[0] - pos[0]; b->tLast = end[0] == zs1; b->tPath = &in.f1; b->tCum = cum[0];
+                    b->tFd2 = zfd2; b->tOff2 = pos[1]; b->tLen2 = end[1] - pos[1]; b->tLast2 = end[1] == zs2; b->tPath2 = &in.f2; b->tCum2 = cum[1];
+                    pos[0] = end[0]; pos[1] = end[1];
+                    const auto tp1 = std::chrono::steady_clock::now();
+                    R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
+                    if (!submit(std::move(b))) { aborted = true; break; }
+                    R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+                    { std::lock_guard<std::mutex> lk(R.tailChain.mu); if (R.zStopped) break; }       // (no run behind a refused one is of use)
+                }
+                if (aborted || !drain()) { aborted = true; break; }
+                if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
+                if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
+                if (R.uptoReached || (!R.zStopped && pos[0] >= zs1 && pos[1] >= zs2)) continue;
+                // the parser pool goes on with both files: from the refused run's first members with that run's heads in front, or from the bytes that are no member
+                resume1 = R.zStopped ? R.zResumeOff : pos[0]; resume2 = R.zStopped ? R.zResumeOff2 : pos[1];
+                resumeHead = R.zStopped ? R.zResumeHead : R.zTail; resumeHead2 = R.zStopped ? R.zResumeHead2 : R.zTail2;
+                resumeId = R.readChain.sum;
+                uint64_t bs = 0, is = 0;
+                for (uint64_t at = resume1; at < zs1 && bgzfMemberAt(zp[0], zs1, at, bs, is); at += bs) zHostMembers++;
+                for (uint64_t at = resume2; at < zs2 && bgzfMemberAt(zp[1], zs2, at, bs, is); at += bs) zHostMembers++;
+            }
         }
         if (R.textCapable && !paired && !o.dumpReads && in.f1 != "-" && ::stat(in.f1.c_str(), &isb) == 0 && S_ISREG(isb.st_mode)) {
             // The device text path: a plain file (not stdin, a pipe or a compressed one) is dealt out to the GPU threads as ranges
@@ -1383,7 +1594,7 @@ int run(int argc, const char **argv) {
                 if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
                 continue;
             }
-            const bool devInflate = !(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE")));
+            const bool devInflate = o.devInflate != 0 && !(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE")));
             if (devInflate && src.bgzfFile(fd, fsize) && fsize) {
                 // A BGZF file: its members are hopped here by their headers (BgzfImpl::fill's test) and dealt out as runs of whole
                 // members, CF_TEXT_BLOCK bytes of compressed plus inflated size at most; the GPU threads have them inflated on the
@@ -1404,18 +1615,7 @@ int run(int argc, const char **argv) {
                 if (zm == MAP_FAILED) die("Error: could not map \"" + in.f1 + "\"");
                 struct Unmap { void *a; size_t n; ~Unmap() { ::munmap(a, n); } } unmap{zm, (size_t)fsize};
                 const unsigned char *z = static_cast<const unsigned char *>(zm);
-                // a member's size in the file and the size of its text; false: not a BGZF member (or one cut short)
-                auto member = [&](uint64_t at, uint64_t &bsize, uint64_t &isize) {
-                    if (fsize - at < 18) return false;
-                    const unsigned char *h = z + at;
-                    const uint64_t xlen = (uint64_t)(h[10] | (h[11] << 8));
-                    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || xlen < 6 || h[12] != 'B' || h[13] != 'C' || h[14] != 2 || h[15] != 0) return false;
-                    bsize = (uint64_t)(h[16] | (h[17] << 8)) + 1;
-                    if (bsize < 12 + xlen + 8 || bsize > fsize - at) return false;
-                    uint32_t v; std::memcpy(&v, h + bsize - 4, 4);
-                    isize = v;
-                    return isize <= 65536;
-                };
+                auto member = [&](uint64_t at, uint64_t &bsize, uint64_t &isize) { return bgzfMemberAt(z, fsize, at, bsize, isize); };
                 uint64_t pos = 0, idx = 0;
                 bool badHeader = false;
                 while (pos < fsize && !R.uptoReached && !badHeader) {
@@ -1460,7 +1660,7 @@ int run(int argc, const char **argv) {
         const bool wantPacked = o.dumpReads ? dumpPacked : !(cfamd::cf_knob("CF_CLI_PACKED") && !std::atoi(cfamd::cf_knob("CF_CLI_PACKED")));
         ChunkedReader s1({in.f1}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume1, resumeHead);
         std::unique_ptr<ChunkedReader> s2;
-        if (paired) s2.reset(new ChunkedReader({in.f2}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume2));
+        if (paired) s2.reset(new ChunkedReader({in.f2}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume2, resumeHead2));
         ReadSoA c1, c2;
         size_t i1 = 0, i2 = 0;
         bool c1Named = false, c2Named = false; // the current chunk of the stream has no unnamed read (bulk path allowed)

@@ -288,6 +288,8 @@ __global__ void __launch_bounds__(64) k_inflate_lane(DInflate d) {
     inflate_body<1>(d, cf_global_thread(), 0, &tables);
 }
 __global__ void k_text_cut(DTextCut c) { if (cf_global_thread() == 0) text_cut_body(c); }
+__global__ void k_text_cut_pair(DTextCutPair c) { if (cf_global_thread() == 0) text_cut_pair_body(c); }
+static_assert(kCutBadStart == kTxBadStart, "the pair cut's flag is the record pass's");
 __global__ void __launch_bounds__(256) k_text_pack(DTextPack d) { text_pack_body(d, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_size(DTextFmt f) { fmt_size_body(f, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_write(DTextFmt f) { fmt_write_body(f, cf_global_thread()); }
@@ -482,6 +484,7 @@ struct cf_batch {
     PinBuf<InfMember> hZMembers;
     PinBuf<uint64_t> hZCut;                  // the inflater's status, the cut, the markers in front of it
     PinBuf<uint8_t> hTail;
+    PinBuf<uint8_t> hTail2;                  // (cf_batch_upload_bgzf_pair: the second file's)
     bool fromText = false;                   // the resident reads came as text (the plan stage packs them: k_text_pack)
     bool rowsStay = false;                   // cf_batch_wait_text: the rows are formatted on the device, none cross the link
     bool textDone = false;                   // ... and have been (a second wait hands the same text back: the tally is made once)
@@ -2155,6 +2158,144 @@ static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf
     zi->tail = reinterpret_cast<const char *>(bt->hTail.p); zi->tail_bytes = total - cut;
 }
 
+// The BGZF members of two mate files (cf_batch_upload_bgzf_pair): the two texts — head + inflate(members) of either file — lie one
+// behind the other in the slot's text buffer as the two blocks of uploadText do, all members are inflated by one launch, and both
+// texts are cut behind the same number of whole records (text_cut_pair_body): nobody knows how many records a run of members holds
+// before it is inflated.  Each file's tail goes back in pinned memory of its own.  The waits are uploadBgzf's.
+static bool bgzfMemberTable(const cf_bgzf_reads *in, uint64_t inAt, uint64_t textAt, InfMember *out, uint64_t &nMembers, uint64_t &total, cf_bgzf_info *zi) {
+    const uint8_t *z = static_cast<const uint8_t *>(in->members);
+    uint64_t at = 0;
+    uint32_t m = 0;
+    total = in->head_bytes;
+    for (; at < in->n_bytes; m++) {
+        const uint8_t *h = z + at;
+        bool ok = in->n_bytes - at >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4);
+        const uint64_t xlen = ok ? (uint64_t)(h[10] | (h[11] << 8)) : 0, bsize = ok ? (uint64_t)(h[16] | (h[17] << 8)) + 1 : 0;
+        ok = ok && xlen >= 6 && h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0 && bsize >= 12 + xlen + 8 && bsize <= in->n_bytes - at;
+        uint32_t crc = 0, isize = 0;
+        if (ok) { std::memcpy(&crc, h + bsize - 8, 4); std::memcpy(&isize, h + bsize - 4, 4); ok = isize <= kInfMaxOut; }
+        if (!ok) { zi->corrupt = kInfHeader; zi->bad_member = m; return false; }
+        if (out) out[m] = InfMember{(uint32_t)(inAt + at + 12 + xlen), (uint32_t)(bsize - 12 - xlen - 8), (uint32_t)(textAt + total), isize, crc};
+        total += isize; at += bsize;
+        if (total >= 0xffff0000ull) throw ArgError("the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
+    }
+    nMembers = m;
+    return true;
+}
+static void uploadBgzfPair(cf_batch *bt, const cf_bgzf_reads *in1, const cf_bgzf_reads *in2, hipStream_t st, cf_text_info *info, cf_bgzf_info *z1, cf_bgzf_info *z2) {
+    const cf_bgzf_reads *in[2] = {in1, in2};
+    cf_bgzf_info *zi[2] = {z1, z2};
+    if (in1->format != CF_TEXT_FASTA && in1->format != CF_TEXT_FASTQ) throw ArgError("cf_bgzf_reads::format is CF_TEXT_FASTA or CF_TEXT_FASTQ");
+    if (in2->format != in1->format || in2->global_seed != in1->global_seed || in2->max_reads != in1->max_reads)
+        throw ArgError("cf_batch_upload_bgzf_pair: format, global_seed and max_reads are the first mate's; the second mate's differ");
+    for (int k = 0; k < 2; k++) {
+        if ((in[k]->n_bytes && !in[k]->members) || (in[k]->head_bytes && !in[k]->head)) throw ArgError("null member / head bytes");
+        if (in[k]->n_bytes >= 0xffff0000ull || in[k]->head_bytes >= 0xffff0000ull) throw ArgError("the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
+    }
+    const uint64_t inAt[2] = {0, (in1->n_bytes + 7) & ~7ull}, inBytes = inAt[1] + in2->n_bytes;
+    if (inBytes >= 0xffff0000ull) throw ArgError("the members of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
+    *info = cf_text_info{}; *z1 = cf_bgzf_info{}; *z2 = cf_bgzf_info{};
+    bt->loaded = false; bt->planned = false; bt->running = false; bt->finished = false;
+    // the members' headers and trailers, first for the sizes (the second text's place follows from the first one's size), then for the table
+    uint64_t nM[2] = {0, 0}, total[2] = {0, 0};
+    for (int k = 0; k < 2; k++) if (!bgzfMemberTable(in[k], 0, 0, nullptr, nM[k], total[k], zi[k])) return;
+    if (total[0] + total[1] >= 0xffff0000ull) throw ArgError("the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
+    const bool fasta = in1->format == CF_TEXT_FASTA;
+    uint64_t at[2], pieces[2], pieceAt[2], recCap[2], posCap[2], posAt[2], textBytes = 0, nPieces = 0, posTotal = 0, recMax = 0;
+    for (int k = 0; k < 2; k++) {
+        at[k] = textBytes; pieces[k] = (total[k] + kTextPiece - 1) / kTextPiece; pieceAt[k] = nPieces;
+        recCap[k] = total[k] / 32 + 1024; posCap[k] = fasta ? recCap[k] : 4 * recCap[k]; posAt[k] = posTotal;
+        textBytes += pieces[k] * kTextPiece + kTextPad; nPieces += pieces[k] + 16; posTotal += posCap[k] + 16;
+        recMax = std::max(recMax, recCap[k]);
+    }
+    if (textBytes >= 0xffffffffull) throw ArgError("the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
+    const uint64_t nMembers = nM[0] + nM[1];
+    bt->hZMembers.ensure(nMembers + 1);
+    for (int k = 0; k < 2; k++) (void)bgzfMemberTable(in[k], inAt[k], at[k], bt->hZMembers.p + (k ? nM[0] : 0), nM[k], total[k], zi[k]);
+    for (int k = 0; k < 2; k++) zi[k]->inflated_bytes = total[k] - in[k]->head_bytes;
+    const uint64_t readCap = 2 * recMax;
+    bt->text.ensure(textBytes);
+    bt->zIn.ensure(inBytes + kInfPad + 8); bt->zMembers.ensure(nMembers + 1); bt->zErr.ensure(nMembers + 1); bt->zSt.ensure(1); bt->zCut.ensure(4);
+    bt->hZCut.ensure(6); bt->hTail.ensure(kBgzfTailRoom + 16); bt->hTail2.ensure(kBgzfTailRoom + 16);
+    bt->txCnt.ensure(nPieces + 16); bt->txBase.ensure(nPieces + 16); bt->txPos.ensure(posTotal + 16);
+    bt->txTileA.ensure(scan_tiles_for(std::max(pieces[0], pieces[1])) + 1); bt->txTileC.ensure(scan_tiles_for(std::max(pieces[0], pieces[1])) + 1);
+    bt->rlen.ensure(readCap + 16); bt->seeds.ensure(readCap + 16);
+    bt->txSeqOff.ensure(readCap + 16); bt->txIdOff.ensure(readCap + 16); bt->txIdLen.ensure(readCap + 16);
+    if (!fasta) bt->txQualOff.ensure(readCap + 16);
+    bt->txSt.ensure(1); bt->hTxSt.ensure(1); bt->hTxTotal.ensure(2);
+    HIP_OK(hipMemsetAsync(bt->txSt.p, 0, sizeof(TextStatus), st));
+    HIP_OK(hipMemsetAsync(bt->zSt.p, 0, sizeof(InfStatus), st));
+    for (int k = 0; k < 2; k++) {
+        uint8_t *text = bt->text.p + at[k];
+        HIP_OK(hipMemsetAsync(text + total[k], 0, pieces[k] * kTextPiece + kTextPad - total[k], st));
+        if (in[k]->head_bytes) HIP_OK(hipMemcpyAsync(text, in[k]->head, in[k]->head_bytes, hipMemcpyHostToDevice, st));
+        if (nM[k]) HIP_OK(hipMemcpyAsync(bt->zIn.p + inAt[k], in[k]->members, in[k]->n_bytes, hipMemcpyHostToDevice, st));
+    }
+    if (nMembers) {
+        HIP_OK(hipMemcpyAsync(bt->zMembers.p, bt->hZMembers.p, nMembers * sizeof(InfMember), hipMemcpyHostToDevice, st));
+        const DInflate d{bt->zIn.p, bt->zMembers.p, (uint32_t)nMembers, bt->text.p, bt->zErr.p, bt->zSt.p, nullptr};
+        hipLaunchKernelGGL(k_inflate, dim3((unsigned)((nMembers + 256 / CF_WAVE - 1) / (256 / CF_WAVE))), dim3(256), 0, st, d);
+    }
+    const dim3 bl(256);
+    DTextCutPair cp{};
+    for (int k = 0; k < 2; k++) {
+        uint8_t *text = bt->text.p + at[k];
+        uint32_t *cnt = bt->txCnt.p + pieceAt[k], *pos = bt->txPos.p + posAt[k];
+        uint64_t *base = bt->txBase.p + pieceAt[k];
+        const DTextMark mk{text, total[k], fasta ? (uint32_t)'>' : (uint32_t)'\n', cnt, base, pos, posCap[k]};
+        const dim3 gp((unsigned)std::max<uint64_t>(1, (pieces[k] + 255) / 256));
+        if (pieces[k]) hipLaunchKernelGGL(k_text_count, gp, bl, 0, st, mk);
+        scan_enqueue<SCAN_PLAIN>(cnt, pieces[k], base, nullptr, bt->txTileA.p, bt->txTileC.p, st);
+        if (pieces[k]) hipLaunchKernelGGL(k_text_mark, gp, bl, 0, st, mk);
+        cp.blk[k] = DTextCut{text, total[k], pos, base + pieces[k], posCap[k], fasta ? 0u : 1u, in[k]->last ? 1u : 0u, bt->zCut.p + 2 * k};
+    }
+    cp.flags = &bt->txSt.p->flags;
+    hipLaunchKernelGGL(k_text_cut_pair, dim3(1), dim3(64), 0, st, cp);
+    HIP_OK(hipMemcpyAsync(bt->hZCut.p, bt->zCut.p, 32, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(bt->hZCut.p + 4, bt->zSt.p, sizeof(InfStatus), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    InfStatus zs; std::memcpy(&zs, bt->hZCut.p + 4, sizeof zs);
+    if (zs.bad) {
+        const uint64_t g = 0xffffffffu - zs.bad;                       // (its number among both files' members)
+        cf_bgzf_info *z = g < nM[0] ? z1 : z2;
+        z->bad_member = (uint32_t)(g < nM[0] ? g : g - nM[0]);
+        HIP_OK(hipMemcpy(&z->corrupt, bt->zErr.p + g, 4, hipMemcpyDeviceToHost));
+        if (!z->corrupt) z->corrupt = kInfBadCode;
+        return;
+    }
+    const uint64_t cut[2] = {bt->hZCut.p[0], bt->hZCut.p[2]}, nMark[2] = {bt->hZCut.p[1], bt->hZCut.p[3]};
+    if (cut[0] > total[0] || cut[1] > total[1]) throw std::runtime_error("cf_batch_upload_bgzf_pair: a cut lies behind its text");
+    // (both texts end here: with as many records in either, both are cut at their ends; else the longer one keeps a tail)
+    if (in1->last && in2->last && (cut[0] < total[0] || cut[1] < total[1])) { info->irregular = kTxMateCount; return; }
+    if (total[0] - cut[0] > kBgzfTailRoom || total[1] - cut[1] > kBgzfTailRoom) { info->irregular = kTxTailRoom; return; }
+    uint8_t *hTail[2] = {bt->hTail.p, bt->hTail2.p};
+    for (int k = 0; k < 2; k++) if (total[k] > cut[k]) HIP_OK(hipMemcpyAsync(hTail[k], bt->text.p + at[k] + cut[k], total[k] - cut[k], hipMemcpyDeviceToHost, st));
+    const uint32_t seed0 = (in1->global_seed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
+    for (int k = 0; k < 2; k++) {
+        const DTextRec d{bt->text.p + at[k], cut[k], bt->txPos.p + posAt[k], bt->zCut.p + 2 * k + 1, posCap[k], (uint32_t)recCap[k], (uint32_t)in1->format, seed0,
+                         bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], 2u, (uint32_t)k,
+                         fasta ? nullptr : bt->txQualOff.p};
+        hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
+    }
+    HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    const TextStatus ts = *bt->hTxSt.p;
+    if (ts.flags) { info->irregular = ts.flags; return; }
+    uint64_t nq = fasta ? nMark[0] : nMark[0] >> 2;
+    if (nq != (fasta ? nMark[1] : nMark[1] >> 2)) throw std::runtime_error("cf_batch_upload_bgzf_pair: the two cuts hold different numbers of records");
+    if (in1->max_reads && nq > in1->max_reads) nq = in1->max_reads;
+    sizeBatch(bt, 2 * nq, ts.words(), ts.bases(), ts.maxLen, true);
+    bindBatch(bt);
+    HIP_OK(hipEventRecord(bt->ev[8], st));
+    bt->fromText = true; bt->fromBytes = false; bt->densePending = 0; bt->revMade = false; bt->nmaskZeroOf = nullptr;
+    bt->textFastq = !fasta;
+    bt->loaded = true;
+    info->n_reads = 2 * nq; info->n_bases = ts.bases(); info->max_len = ts.maxLen;
+    for (int k = 0; k < 2; k++) { zi[k]->tail = reinterpret_cast<const char *>(hTail[k]); zi[k]->tail_bytes = total[k] - cut[k]; }
+}
+
 // ======================================================================= batch C ABI
 cf_status cf_host_alloc(void **p, size_t bytes) {
     if (!p) return CF_ERR_ARG;
@@ -2367,6 +2508,15 @@ cf_status cf_batch_upload_bgzf(cf_batch *bt, const cf_bgzf_reads *in, void *stre
         HIP_OK(hipSetDevice(bt->cl->ix->device));
         if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
         uploadBgzf(bt, in, static_cast<hipStream_t>(streamv), info, zi);
+    });
+}
+
+cf_status cf_batch_upload_bgzf_pair(cf_batch *bt, const cf_bgzf_reads *mate1, const cf_bgzf_reads *mate2, void *streamv, cf_text_info *info, cf_bgzf_info *z1, cf_bgzf_info *z2) {
+    if (!bt || !mate1 || !mate2 || !info || !z1 || !z2) return CF_ERR_ARG;
+    return guard([&] {
+        HIP_OK(hipSetDevice(bt->cl->ix->device));
+        if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
+        uploadBgzfPair(bt, mate1, mate2, static_cast<hipStream_t>(streamv), info, z1, z2);
     });
 }
 

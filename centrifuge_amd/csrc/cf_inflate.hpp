@@ -340,4 +340,39 @@ CF_DEV void text_cut_body(const DTextCut &c) {
     c.cut[0] = cut; c.cut[1] = k;
 }
 
+// ---- mates: the texts of the two files of a BGZF pair upload are cut at a COMMON record.  Block i holds k_i whole records under
+// the rule above (with its own `last`); n = min(k_0, k_1) records of either go through, so block i is cut behind its record n:
+//   a block with k_i == n   the cut of the rule above (and what that rule says of a last text that does not end a record)
+//   FASTQ                   behind '\n' number 4 n (0: the text's start)
+//   FASTA                   in front of '>' number n, which has to start the text or follow a '\n': one that does not makes the
+//                           block irregular (kCutBadStart into *flags) — nothing is guessed
+// A block with more markers than are kept keeps the cut of the rule above, and the record pass refuses it.  One thread, as above.
+constexpr uint32_t kCutBadStart = 1u;                   // (kTxBadStart of cf_textio.hpp)
+struct DTextCutPair {
+    DTextCut blk[2];             // blk[i].cut: [0] block i's cut, [1] the markers in front of it
+    uint32_t *flags;             // TextStatus::flags
+};
+CF_DEV void text_cut_pair_body(const DTextCutPair &c) {
+    uint64_t own0[2], own1[2];
+    DTextCut s0 = c.blk[0], s1 = c.blk[1];
+    s0.cut = own0; s1.cut = own1;
+    text_cut_body(s0); text_cut_body(s1);
+    const uint64_t k0 = s0.fastq ? own0[1] >> 2 : own0[1], k1 = s1.fastq ? own1[1] >> 2 : own1[1];
+    const uint64_t n = k0 < k1 ? k0 : k1;
+#pragma unroll
+    for (uint32_t i = 0; i < 2; i++) {
+        const DTextCut &b = c.blk[i];
+        uint64_t cut = i ? own1[0] : own0[0], markers = i ? own1[1] : own0[1];
+        if (*b.total <= b.posCap && n != (i ? k1 : k0)) {
+            if (b.fastq) { markers = 4 * n; cut = n ? (uint64_t)b.pos[4 * n - 1] + 1 : 0; }
+            else {
+                const uint32_t p = b.pos[n];
+                if (p != 0 && b.text[p - 1] != '\n') cf_atomic_or(c.flags, kCutBadStart);
+                markers = n; cut = p;
+            }
+        }
+        b.cut[0] = cut; b.cut[1] = markers;
+    }
+}
+
 }  // namespace cfamd

@@ -341,6 +341,25 @@ typedef struct {
     uint64_t inflated_bytes; uint32_t corrupt;  uint32_t bad_member;
 } cf_bgzf_info;
 cf_status cf_batch_upload_bgzf(cf_batch *, const cf_bgzf_reads *, void *hip_stream, cf_text_info *, cf_bgzf_info *);
+/* The BGZF files of MATES (-1 / -2): runs of whole members of the two files in one call.  Either text is  head_i + inflate(members_i),
+ * starts at a record start and — as nobody knows how many records a run of members holds before it is inflated — both are CUT on
+ * the device behind the SAME number of whole records:
+ *   k_i    the whole records of text i under the rule above, with mate_i's own `last`
+ *   n      min(k_1, k_2): the records of either text that go through
+ *   FASTQ  text i is cut behind the '\n' whose count from its start is 4 n
+ *   FASTA  text i is cut in front of its '>' number n (from 0); a text with k_i == n is cut by the rule above.  A '>' number n that
+ *          neither starts the text nor follows a '\n' makes the call `irregular` (bit 1 of info->irregular): nothing is guessed
+ *   last   both texts end and k_1 != k_2: the files hold different numbers of records, info->irregular has CF_TEXT_MATE_COUNT set
+ * info->n_reads is 2 n: reads 2q and 2q+1 of the batch are the mates of query q, as with cf_text_reads::text2; what lies behind
+ * the cuts comes back as mate_i's tail (z1->tail, z2->tail; 1 MiB of room each), to be handed in as the next call's heads.  format,
+ * global_seed and max_reads (which counts pairs) are mate1's: a mate2 that disagrees is CF_ERR_ARG; members, head and last are each
+ * struct's own.  A file that has run out of members goes on with n_bytes 0 and last 1 while the other one still has some.  A call
+ * in which either side has no whole record is legal: n_reads == 0, both texts come back as the tails.  The refusals are those of
+ * cf_batch_upload_bgzf (the size limit holds for the two texts together; a corrupt member is reported in the file it belongs to:
+ * z1 or z2), and cf_batch_wait_text and cf_batch_set_text_columns work on the batch. */
+#define CF_TEXT_MATE_COUNT 2048u
+cf_status cf_batch_upload_bgzf_pair(cf_batch *, const cf_bgzf_reads *mate1, const cf_bgzf_reads *mate2, void *hip_stream, cf_text_info *info,
+                                    cf_bgzf_info *z1, cf_bgzf_info *z2);
 /* Out: the batch's rows as text — by default the columns centrifuge prints by default, readID seqID taxID score 2ndBestScore
  * hitLength queryLength numMatches; any other list after cf_batch_set_text_columns —, one line per row, query order, formatted on the device from the rows the kernels left there (no row crosses the
  * link) with the readIDs copied out of the uploaded block; in the slot's pinned memory, valid until its next upload.  Needs the
