@@ -231,6 +231,7 @@ def lib():
         "cf_batch_upload_bgzf_pair": (i32, [vp, C.POINTER(BgzfReads), C.POINTER(BgzfReads), vp, C.POINTER(TextInfo), C.POINTER(BgzfInfo), C.POINTER(BgzfInfo)]),
         "cf_batch_wait_text": (i32, [vp, C.POINTER(ResultsText)]),
         "cf_text_column_of": (C.c_int32, [cp]), "cf_batch_set_text_columns": (i32, [vp, vp, u32]),
+        "cf_batch_set_text_trim": (i32, [vp, u32, u32]), "cf_batch_set_text_skip": (i32, [vp, u64]),
         "cf_counts_get_single": (i32, [vp, vp]),
         "cf_report_add_tuples": (i32, [vp, vp, u64]), "cf_report_adopt_device_tally": (i32, [vp, vp, vp, vp, u64]),
         "cf_batch_set_limits": (i32, [vp, u64, u64]),
@@ -678,6 +679,15 @@ class Slot:
                 codes.append(int(c))
         a = np.asarray(codes, dtype=np.int32)
         _check(self.L.cf_batch_set_text_columns(self.h, a.ctypes.data if len(a) else None, len(a)))
+
+    def set_text_trim(self, trim5, trim3):
+        """-5 / -3 for the slot's later submit_text / submit_bgzf / submit_bgzf_pair calls: a read is its record's bases without the
+        first trim5 and the last trim3 of them (a record of which nothing is left makes its block irregular)"""
+        _check(self.L.cf_batch_set_text_trim(self.h, int(trim5), int(trim3)))
+
+    def set_text_skip(self, n):
+        """-s for the slot's later text submits: the first n records (pairs, for mates) of each are dropped, before max_reads counts"""
+        _check(self.L.cf_batch_set_text_skip(self.h, int(n)))
 
     def wait_text(self):
         """-> the batch's rows as text (bytes; the default columns, or those of set_text_columns), the perfect multi-assignment tuples (u32: n, n taxon indices, ...), info"""

@@ -96,7 +96,7 @@ void usage(std::FILE *f) {
         "          text and the rows come back as text, formatted on the device — the default columns, any --tab-fmt-cols list of up\n"
         "          to 32 columns, --out-fmt sam — same bytes either way; an unpaired BGZF .gz file (bgzip, htslib) goes up compressed and\n"
         "          is inflated on the device, the parser pool taking the file over at its first record outside the plain form; BGZF mates,\n"
-        "          other .gz files, .bz2, stdin, -s and -5/-3 keep the host threads)\n"
+        "          other .gz files, .bz2 and stdin keep the host threads; -5/-3 and -s/-u do not: trimming and skipping happen on the device)\n"
         "          --device-inflate <off|unpaired|all> (which BGZF inputs are inflated on the device: none, an unpaired file (default),\n"
         "          or also a -1/-2 pair of BGZF files — both texts are cut behind a common record on the device —, the parser pool\n"
         "          taking both files over at the first run the device refuses)\n"
@@ -747,12 +747,12 @@ struct Runner {
             // the host parser's semantics are the reference's for every record: this block alone pays for what it holds
             b.r.clear(); b.r.hasQual = false;
             try {
-                if (fasta) parseFastaChunk(g.tin, g.tin + b.tLen, b.tFirst, 0, 0, o.seed, b.r, b.tLast);
-                else parseFastqChunk(g.tin, g.tin + b.tLen, b.tFirst, 0, 0, o.seed, b.r, b.tLast);
+                if (fasta) parseFastaChunk(g.tin, g.tin + b.tLen, b.tFirst, o.trim5, o.trim3, o.seed, b.r, b.tLast);
+                else parseFastqChunk(g.tin, g.tin + b.tLen, b.tFirst, o.trim5, o.trim3, o.seed, b.r, b.tLast);
                 if (mates) {
                     b.r2.clear(); b.r2.hasQual = false;
-                    if (fasta) parseFastaChunk(g.tin + at2, g.tin + at2 + b.tLen2, b.tFirst, 0, 0, o.seed, b.r2, b.tLast);
-                    else parseFastqChunk(g.tin + at2, g.tin + at2 + b.tLen2, b.tFirst, 0, 0, o.seed, b.r2, b.tLast);
+                    if (fasta) parseFastaChunk(g.tin + at2, g.tin + at2 + b.tLen2, b.tFirst, o.trim5, o.trim3, o.seed, b.r2, b.tLast);
+                    else parseFastqChunk(g.tin + at2, g.tin + at2 + b.tLen2, b.tFirst, o.trim5, o.trim3, o.seed, b.r2, b.tLast);
                 }
             } catch (const std::exception &e) {
                 // a record the parser refuses: the run ends with the message of the FIRST such record of the file, as the reference's
@@ -775,15 +775,20 @@ struct Runner {
         // the ordinal of the block's first read: -u, and the names of reads that have none (pat.cpp:838-842)
         const uint64_t base = readChain.enter(b.tIdx);
         readChain.leave(nReads);
-        const uint64_t take = base >= o.upto ? 0 : std::min<uint64_t>(nReads, o.upto - base);
+        // -s / -u: the block's records [drop, drop + take) are printed (o.upto counts from the file's start: it includes o.skip)
+        const uint64_t drop = base >= o.skip ? 0 : std::min<uint64_t>(nReads, o.skip - base);
+        const uint64_t upTo = base >= o.upto ? 0 : std::min<uint64_t>(nReads, o.upto - base);
+        const uint64_t take = upTo > drop ? upTo - drop : 0;
         if (base + nReads >= o.upto) uptoReached = true;
         const char *text = "";
         uint64_t nText = 0;
         if (take == 0) { /* (past -u: nothing of this block is printed) */ }
         else if (!onHost) {
-            if (take < nReads) {                                        // the block -u ends in: once more, its first reads only
-                in.max_reads = take;
+            if (take < nReads) {                                        // the block -s ends in or -u ends in: once more, those reads only
+                in.max_reads = upTo < nReads ? take : 0;
+                CF_TRY(cf_batch_set_text_skip(g.slot, drop));
                 CF_TRY(cf_batch_upload_text(g.slot, &in, g.stream, &info));
+                CF_TRY(cf_batch_set_text_skip(g.slot, 0));
                 if (info.irregular || info.n_reads != take * per) die("internal error: a block changed between two parses");
             }
             CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
@@ -799,7 +804,7 @@ struct Runner {
         } else {
             g.hostBlocks++;
             if (mates || take < nReads || b.r.hasEmptyName()) {
-                // reads past -u go, reads without a name are named after their ordinal, mates are laid side by side: the block's records one by one
+                // reads in front of -s and past -u go, reads without a name are named after their ordinal, mates are laid side by side: the block's records one by one
                 ReadSoA src;
                 std::swap(src, b.r);
                 b.r.clear(); b.r.hasQual = false;
@@ -810,7 +815,7 @@ struct Runner {
                     const uint8_t *q = c.hasQual ? c.qual.data() + c.off[i] : nullptr;
                     b.r.push(c.seq.data() + c.off[i], q, len, nm.data(), nm.size(), cf_gen_rand_seed(c.seq.data() + c.off[i], q, len, nm.data(), nm.size(), o.seed));
                 };
-                for (uint64_t i = 0; i < take; i++) { one(src, i); if (mates) one(b.r2, i); }
+                for (uint64_t i = drop; i < drop + take; i++) { one(src, i); if (mates) one(b.r2, i); }
             }
             b.r.pack();
             b.paired = mates;
@@ -911,14 +916,18 @@ struct Runner {
         const uint64_t nReads = skip ? 0 : info.n_reads;
         const uint64_t base = readChain.enter(b.tIdx);
         readChain.leave(nReads);
-        const uint64_t take = base >= o.upto ? 0 : std::min<uint64_t>(nReads, o.upto - base);
+        const uint64_t drop = base >= o.skip ? 0 : std::min<uint64_t>(nReads, o.skip - base);     // (-s / -u: as in classifyText)
+        const uint64_t upTo = base >= o.upto ? 0 : std::min<uint64_t>(nReads, o.upto - base);
+        const uint64_t take = upTo > drop ? upTo - drop : 0;
         if (!skip && base + nReads >= o.upto) uptoReached = true;
         const char *text = "";
         uint64_t nText = 0;
         if (take) {
-            if (take < nReads) {                                        // the run -u ends in: once more, its first reads only
-                in.max_reads = take;
+            if (take < nReads) {                                        // the run -s ends in or -u ends in: once more, those reads only
+                in.max_reads = upTo < nReads ? take : 0;
+                CF_TRY(cf_batch_set_text_skip(g.slot, drop));
                 CF_TRY(cf_batch_upload_bgzf(g.slot, &in, g.stream, &info, &zi));
+                CF_TRY(cf_batch_set_text_skip(g.slot, 0));
                 if (info.irregular || zi.corrupt || info.n_reads != take) die("internal error: a run of members changed between two uploads");
             }
             CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
@@ -990,14 +999,18 @@ struct Runner {
         const uint64_t nPairs = skip ? 0 : info.n_reads / 2;
         const uint64_t base = readChain.enter(b.tIdx);
         readChain.leave(nPairs);
-        const uint64_t take = base >= o.upto ? 0 : std::min<uint64_t>(nPairs, o.upto - base);
+        const uint64_t drop = base >= o.skip ? 0 : std::min<uint64_t>(nPairs, o.skip - base);     // (-s / -u: as in classifyText)
+        const uint64_t upTo = base >= o.upto ? 0 : std::min<uint64_t>(nPairs, o.upto - base);
+        const uint64_t take = upTo > drop ? upTo - drop : 0;
         if (!skip && base + nPairs >= o.upto) uptoReached = true;
         const char *text = "";
         uint64_t nText = 0;
         if (take) {
-            if (take < nPairs) {                                        // the run -u ends in: once more, its first pairs only
-                in1.max_reads = in2.max_reads = take;
+            if (take < nPairs) {                                        // the run -s ends in or -u ends in: once more, those pairs only
+                in1.max_reads = in2.max_reads = upTo < nPairs ? take : 0;
+                CF_TRY(cf_batch_set_text_skip(g.slot, drop));
                 CF_TRY(cf_batch_upload_bgzf_pair(g.slot, &in1, &in2, g.stream, &info, &z1, &z2));
+                CF_TRY(cf_batch_set_text_skip(g.slot, 0));
                 if (info.irregular || z1.corrupt || z2.corrupt || info.n_reads != 2 * take) die("internal error: a run of members changed between two uploads");
             }
             CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
@@ -1264,11 +1277,11 @@ int run(int argc, const char **argv) {
         p.host_taxids = o.hostTaxids.data(); p.n_host = (int32_t)o.hostTaxids.size();
         p.exclude_taxids = o.excludeTaxids.data(); p.n_exclude = (int32_t)o.excludeTaxids.size();
         for (auto &d : R.devs) CF_TRY(cf_classifier_create(d.ix, &p, &d.clf));
-        // The device text path (round 6): whole blocks of a plain FASTA / FASTQ file up as text, the rows back as text — without
-        // trimming or a skip, up to CF_TEXT_MAX_COLS columns (cf_batch_set_text_columns), -k <= 63 (the narrow rows' six bits).  Every GPU thread
+        // The device text path (round 6): whole blocks of a plain FASTA / FASTQ file up as text, the rows back as text — with
+        // -5 / -3 as the record pass's window (cf_batch_set_text_trim), -s / -u by the block (cf_batch_set_text_skip, max_reads), up to CF_TEXT_MAX_COLS columns (cf_batch_set_text_columns), -k <= 63 (the narrow rows' six bits).  Every GPU thread
         // then also reads its blocks and writes its text, so there are more of them (each with a slot on the device).
         R.textCapable = !ordered && o.cols.size() <= CF_TEXT_MAX_COLS && (o.format == ReadFormat::Fasta || o.format == ReadFormat::Fastq) &&
-                        o.trim5 == 0 && o.trim3 == 0 && o.skip == 0 && o.khits <= 63 && !o.hostIo &&
+                        o.khits <= 63 && !o.hostIo &&
                         !(cfamd::cf_knob("CF_CLI_DEVICE_TEXT") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_TEXT")));
         const int slots = ordered ? 1 : (R.textCapable && !o.slotsSet) ? std::max(2, std::min(6, o.threads / 2)) : o.slots;
         R.gts.resize(R.devs.size() * (size_t)slots);
@@ -1281,6 +1294,7 @@ int run(int argc, const char **argv) {
                 const std::vector<int32_t> prog(o.cols.begin(), o.cols.end());
                 CF_TRY(cf_batch_set_text_columns(g.slot, prog.data(), (uint32_t)prog.size()));
             }
+            if (R.textCapable && (o.trim5 > 0 || o.trim3 > 0)) CF_TRY(cf_batch_set_text_trim(g.slot, (uint32_t)std::max(0, o.trim5), (uint32_t)std::max(0, o.trim3)));
             if (!ordered) CF_TRY(cf_report_create(R.ix, &g.rep));
         }
         if (R.textCapable) { for (size_t t = 0; t < R.gts.size(); t++) R.hostOut.push_back(new Runner::OutBuf()); }

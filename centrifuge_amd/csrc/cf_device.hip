@@ -466,6 +466,7 @@ struct cf_batch {
     // formatted rows
     DevBuf<uint8_t> text, textOut;
     DevBuf<uint32_t> txCnt, txPos, txSeqOff, txIdOff, txIdLen, txQualOff, txSize, txTuples, txTileC;
+    uint32_t textTrim5 = 0, textTrim3 = 0, textSkip = 0;   // cf_batch_set_text_trim / cf_batch_set_text_skip: what the record pass of the slot's later text uploads is launched with
     TextCols textCols{};                     // cf_batch_set_text_columns: the columns cf_batch_wait_text prints (nCols 0: the default eight, by the default kernels)
     bool textFastq = false;                  // the block that is loaded is FASTQ (txQualOff holds its quality lines' places)
     DevBuf<uint64_t> txBase, txOutOff, txTileA;
@@ -2031,7 +2032,7 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
         if (pieces[k]) hipLaunchKernelGGL(k_text_mark, gp, bl, 0, st, m);
         DTextRec d{text, nBs[k], pos, base + pieces[k], posCap[k], (uint32_t)recCap[k], (uint32_t)in->format, seed0,
                    bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], (uint32_t)nBlocks, (uint32_t)k,
-                   fasta ? nullptr : bt->txQualOff.p};
+                   fasta ? nullptr : bt->txQualOff.p, bt->textTrim5, bt->textTrim3, bt->textSkip};
         hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
         HIP_OK(hipMemcpyAsync(bt->hTxTotal.p + k, base + pieces[k], 8, hipMemcpyDeviceToHost, st));
     }
@@ -2043,7 +2044,7 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
     for (int k = 0; k < nBlocks; k++) nRec[k] = fasta ? bt->hTxTotal.p[k] : bt->hTxTotal.p[k] >> 2;
     if (ts.flags) { info->irregular = ts.flags; return; }
     if (nBlocks == 2 && nRec[0] != nRec[1]) { info->irregular = kTxMateCount; return; }
-    uint64_t nq = nRec[0];
+    uint64_t nq = nRec[0] - std::min<uint64_t>(nRec[0], bt->textSkip);  // (cf_batch_set_text_skip: dropped before max_reads counts)
     if (in->max_reads && nq > in->max_reads) nq = in->max_reads;     // (the sums below then cover a few reads too many: upper bounds, as they may be)
     const uint64_t nReads = nq * (uint64_t)nBlocks;
     sizeBatch(bt, nReads, ts.words(), ts.bases(), ts.maxLen, nBlocks == 2);
@@ -2139,7 +2140,8 @@ static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf
     if (total > cut) HIP_OK(hipMemcpyAsync(bt->hTail.p, text + cut, total - cut, hipMemcpyDeviceToHost, st));
     const uint32_t seed0 = (in->global_seed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
     const DTextRec d{text, cut, bt->txPos.p, bt->zCut.p + 1, posCap, (uint32_t)recCap, (uint32_t)in->format, seed0,
-                     bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, 0u, 1u, 0u, fasta ? nullptr : bt->txQualOff.p};
+                     bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, 0u, 1u, 0u, fasta ? nullptr : bt->txQualOff.p,
+                     bt->textTrim5, bt->textTrim3, bt->textSkip};
     hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap + 255) / 256)), bl, 0, st, d);
     HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -2147,6 +2149,7 @@ static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf
     const TextStatus ts = *bt->hTxSt.p;
     if (ts.flags) { info->irregular = ts.flags; return; }
     uint64_t nq = fasta ? bt->hZCut.p[1] : bt->hZCut.p[1] >> 2;
+    nq -= std::min<uint64_t>(nq, bt->textSkip);
     if (in->max_reads && nq > in->max_reads) nq = in->max_reads;
     sizeBatch(bt, nq, ts.words(), ts.bases(), ts.maxLen, false);
     bindBatch(bt);
@@ -2275,7 +2278,7 @@ static void uploadBgzfPair(cf_batch *bt, const cf_bgzf_reads *in1, const cf_bgzf
     for (int k = 0; k < 2; k++) {
         const DTextRec d{bt->text.p + at[k], cut[k], bt->txPos.p + posAt[k], bt->zCut.p + 2 * k + 1, posCap[k], (uint32_t)recCap[k], (uint32_t)in1->format, seed0,
                          bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], 2u, (uint32_t)k,
-                         fasta ? nullptr : bt->txQualOff.p};
+                         fasta ? nullptr : bt->txQualOff.p, bt->textTrim5, bt->textTrim3, bt->textSkip};
         hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
     }
     HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
@@ -2285,6 +2288,7 @@ static void uploadBgzfPair(cf_batch *bt, const cf_bgzf_reads *in1, const cf_bgzf
     if (ts.flags) { info->irregular = ts.flags; return; }
     uint64_t nq = fasta ? nMark[0] : nMark[0] >> 2;
     if (nq != (fasta ? nMark[1] : nMark[1] >> 2)) throw std::runtime_error("cf_batch_upload_bgzf_pair: the two cuts hold different numbers of records");
+    nq -= std::min<uint64_t>(nq, bt->textSkip);
     if (in1->max_reads && nq > in1->max_reads) nq = in1->max_reads;
     sizeBatch(bt, 2 * nq, ts.words(), ts.bases(), ts.maxLen, true);
     bindBatch(bt);
@@ -2605,6 +2609,19 @@ cf_status cf_batch_set_text_columns(cf_batch *bt, const int32_t *cols, uint32_t 
     static const uint8_t kDefault[8] = {kColReadId, kColSeqId, kColTaxId, kColScore, kColScore2, kColHitLen, kColQueryLen, kColNumMatches};
     if (nCols == 8 && !std::memcmp(pc.col, kDefault, 8)) pc = TextCols{};
     bt->textCols = pc;
+    return CF_OK;
+}
+
+// -5 / -3 and -s of the text uploads: kept in the slot, handed to the record pass (DTextRec) by the slot's later uploads
+cf_status cf_batch_set_text_trim(cf_batch *bt, uint32_t trim5, uint32_t trim3) {
+    static_assert(CF_TEXT_EMPTY_SEQ == kTxEmptySeq, "the public bit is the kernels'");
+    if (!bt) return CF_ERR_ARG;
+    bt->textTrim5 = trim5; bt->textTrim3 = trim3;
+    return CF_OK;
+}
+cf_status cf_batch_set_text_skip(cf_batch *bt, uint64_t skipReads) {
+    if (!bt) return CF_ERR_ARG;
+    bt->textSkip = (uint32_t)std::min<uint64_t>(skipReads, 0xffffffffull);   // (a block holds fewer than 2^32 records: beyond that, all of them go)
     return CF_OK;
 }
 

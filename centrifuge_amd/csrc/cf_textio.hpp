@@ -123,6 +123,11 @@ struct DTextRec {
     // later passes count from the buffer's start), record r of block `mate` is read stride * r + mate of the batch
     uint32_t textBase, stride, mate;
     uint32_t *qualOff;           // FASTQ: first byte of the record's quality line (nullptr: not kept; the readQual columns of fmt_cols_write_body)
+    // -5 / -3 / -s (cf_batch_set_text_trim, cf_batch_set_text_skip; all zero: none of it).  A read is the window of its record's
+    // bases behind the first trim5 and in front of the last trim3 of them (pat.cpp: the parsers' trimming) — rlen, seeds, seqOff,
+    // qualOff and the block's sums speak of the window, the plain-form checks of the whole record.  The block's first `skip`
+    // records are checked and leave nothing else behind: record r >= skip is read stride * (r - skip) + mate of the batch.
+    uint32_t trim5, trim3, skip;
 };
 CF_DEV bool tx_isspace(uint32_t c) { return c == ' ' || (c >= 9 && c <= 13); }
 // base letter -> 0..3, 4 = N, 5 = not a plain base letter
@@ -184,6 +189,53 @@ CF_DEV uint32_t tx_bases(const uint8_t *text, uint64_t pos, uint64_t e, uint32_t
     }
     return 0;
 }
+// the byte of base number n of a record whose bases start at byte `pos` (line ends stepped over; `e` when it has no more than n)
+CF_DEV uint64_t tx_skip_bases(const uint8_t *text, uint64_t pos, uint64_t e, uint32_t n) {
+    uint32_t i = 0;
+    while (pos < e) {
+        const uint64_t x = tx_load8(text, pos);
+        if (n - i >= 8 && e - pos >= 8 && tx_match8(x, '\n') == 0) { i += 8; pos += 8; continue; }
+        if (((uint32_t)x & 0xffu) == '\n') { pos++; continue; }
+        if (i == n) break;                                               // (the first kept base, not a line end in front of it)
+        i++; pos++;
+    }
+    return pos;
+}
+// the seed's term of the n bases from byte `pos` on (line ends skipped; never past `e`), the first of them base number 0: the window
+// of a trimmed record, whose letters tx_bases has checked
+CF_DEV uint32_t tx_bases_window(const uint8_t *text, uint64_t pos, uint64_t e, uint32_t n, uint32_t &seed) {
+    uint32_t i = 0;
+    while (i < n && pos < e) {
+        const uint64_t x = tx_load8(text, pos);
+        if (n - i >= 8 && e - pos >= 8) {
+            uint32_t c16, n8, bad8, nl8;
+            tx_codes8(x, c16, n8, bad8, nl8);
+            if (nl8 == 0) { seed ^= tx_seed8(c16, n8, i); i += 8; pos += 8; continue; }
+        }
+        const uint32_t ch = (uint32_t)x & 0xffu;
+        pos++;
+        if (ch == '\n') continue;
+        const uint32_t code = tx_code(ch);
+        seed ^= (code > 4 ? 0u : code) << ((i & 15u) << 1);               // (no plain letter: the block is refused anyway)
+        i++;
+    }
+    return i;
+}
+// the quality characters from byte `pos` to byte `e` of one line: their term of the seed (r ^= q[j] << 8(j mod 4), the first of them
+// j = 0: the string's little-endian dwords folded together), kTxBadQual when one of them is below 33
+CF_DEV uint32_t tx_quals(const uint8_t *text, uint64_t pos, uint64_t e, uint32_t &seed) {
+    uint32_t flags = 0, j = 0;
+    while (pos < e) {
+        uint64_t x = tx_load8(text, pos);
+        const uint32_t take = e - pos >= 8 ? 8u : (uint32_t)(e - pos);
+        if (take < 8) x = (x & ((1ull << (8 * take)) - 1)) | (0x2121212121212121ull << (8 * take));   // (the bytes past the line: no offence, and folded out again)
+        if (tx_below33(x)) flags |= kTxBadQual;
+        if (take < 8) x &= (1ull << (8 * take)) - 1;
+        seed ^= tx_rotl32((uint32_t)x ^ (uint32_t)(x >> 32), 8u * (j & 3u));
+        j += take; pos += take;
+    }
+    return flags;
+}
 // the name line from `from` to its '\n' (which must lie before `lim`): the name's term of the seed, the readID's length
 CF_DEV uint32_t tx_name(TxCursor &c, uint64_t lim, uint32_t &r, uint32_t &nameLen, uint32_t &idLen) {
     uint32_t flags = 0, j = 0, ws = 0xffffffffu, p1 = 0, p2 = 0;
@@ -228,17 +280,30 @@ CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
             if (tc.nRec == 0) flags |= kTxBadStart;
         }
     }
-    const uint64_t w = (uint64_t)d.stride * r + d.mate;                 // the read's number in the batch
+    // -s: the block's first records are checked like the others and leave nothing behind
+    const bool kept = live && r >= d.skip;
+    const uint64_t w = (uint64_t)d.stride * (r - d.skip) + d.mate;      // the read's number in the batch
+    const bool trim = (d.trim5 | d.trim3) != 0;                         // (the same for every thread of the launch)
     if (live) {
-        uint32_t seed = d.seed0, nameLen = 0, idLen = 0;
+        uint32_t seed = d.seed0, nameLen = 0, idLen = 0, idOff, seqOff, qualOff = 0;
         TxCursor c;
         if (d.format == kTextFasta) {
             const uint64_t s = d.pos[r], e = r + 1 < tc.nRec ? (uint64_t)d.pos[r + 1] : d.nBytes;
             c.seek(d.text, s + 1);
             flags |= tx_name(c, e, seed, nameLen, idLen);
-            d.idOff[w] = d.textBase + (uint32_t)(s + 1); d.idLen[w] = idLen;
-            d.seqOff[w] = d.textBase + (uint32_t)c.at;
-            flags |= tx_bases(d.text, c.at, e, seed, len);
+            idOff = (uint32_t)(s + 1);
+            if (!trim) {
+                seqOff = (uint32_t)c.at;
+                flags |= tx_bases(d.text, c.at, e, seed, len);
+            } else {
+                // -3 needs the record's length first: once over the record for the checks and the count, once over the window
+                uint32_t all = 0, unused = 0;
+                flags |= tx_bases(d.text, c.at, e, unused, all);
+                const uint32_t t5 = d.trim5 < all ? d.trim5 : all, keep = all - t5 > d.trim3 ? all - t5 - d.trim3 : 0u;
+                const uint64_t first = tx_skip_bases(d.text, c.at, e, t5);
+                seqOff = (uint32_t)first;
+                len = tx_bases_window(d.text, first, e, keep, seed);
+            }
             // the qualities of a FASTA read are 'I' throughout: their term depends on the length only
             uint32_t q = ((len >> 2) & 1u) ? 0x49494949u : 0u;
             for (uint32_t j = 0; j < (len & 3u); j++) q ^= 0x49u << (j << 3);
@@ -249,33 +314,44 @@ CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
             if (d.text[ls] != '@') flags |= kTxBadStart;
             c.seek(d.text, ls + 1);
             flags |= tx_name(c, n0 + 1, seed, nameLen, idLen);
-            d.idOff[w] = d.textBase + (uint32_t)(ls + 1); d.idLen[w] = idLen;
-            d.seqOff[w] = d.textBase + (uint32_t)(n0 + 1);
-            flags |= tx_bases(d.text, n0 + 1, n1, seed, len);
-            if (d.qualOff) d.qualOff[w] = d.textBase + (uint32_t)(n2 + 1);
+            idOff = (uint32_t)(ls + 1);
             if (n2 <= n1 + 1 || d.text[n1 + 1] != '+') flags |= kTxBadPlus;
-            if (n3 - n2 != n1 - n0) flags |= kTxQualLen;
-            else {
-                // the qualities' term (r ^= q[j] << 8(j mod 4)): the string's little-endian dwords folded together
-                uint64_t pos = n2 + 1;
-                uint32_t j = 0;
-                while (pos < n3) {
-                    uint64_t x = tx_load8(d.text, pos);
-                    const uint32_t take = n3 - pos >= 8 ? 8u : (uint32_t)(n3 - pos);
-                    if (take < 8) x = (x & ((1ull << (8 * take)) - 1)) | (0x2121212121212121ull << (8 * take));   // (the bytes past the line: no offence, and folded out again)
-                    if (tx_below33(x)) flags |= kTxBadQual;
-                    if (take < 8) x &= (1ull << (8 * take)) - 1;
-                    seed ^= tx_rotl32((uint32_t)x ^ (uint32_t)(x >> 32), 8u * (j & 3u));
-                    j += take; pos += take;
+            if (!trim) {
+                seqOff = (uint32_t)(n0 + 1); qualOff = (uint32_t)(n2 + 1);
+                flags |= tx_bases(d.text, n0 + 1, n1, seed, len);
+                if (n3 - n2 != n1 - n0) flags |= kTxQualLen;
+                else flags |= tx_quals(d.text, n2 + 1, n3, seed);
+            } else {
+                // one line each: the window is a stretch of it — its terms of the seed start over at the window's first base; the
+                // parts in front of it and behind it are checked only
+                const uint64_t all = n1 > n0 ? n1 - n0 - 1 : 0;
+                const uint64_t t5 = d.trim5 < all ? d.trim5 : all, keep = all - t5 > d.trim3 ? all - t5 - d.trim3 : 0;
+                const uint64_t b0 = n0 + 1 + t5, b1 = b0 + keep;
+                uint32_t unused = 0, cnt = 0;
+                seqOff = (uint32_t)b0; qualOff = (uint32_t)(n2 + 1 + t5);
+                flags |= tx_bases(d.text, n0 + 1, b0, unused, cnt);
+                flags |= tx_bases(d.text, b0, b1, seed, len);
+                flags |= tx_bases(d.text, b1, n1, unused, cnt);
+                if (n3 - n2 != n1 - n0) flags |= kTxQualLen;
+                else {
+                    const uint64_t q0 = n2 + 1 + t5, q1 = q0 + keep;
+                    flags |= tx_quals(d.text, n2 + 1, q0, unused);
+                    flags |= tx_quals(d.text, q0, q1, seed);
+                    flags |= tx_quals(d.text, q1, n3, unused);
                 }
             }
         }
         if (len == 0) flags |= kTxEmptySeq;
-        d.rlen[w] = len; d.seeds[w] = seed;
+        if (kept) {
+            d.idOff[w] = d.textBase + idOff; d.idLen[w] = idLen;
+            d.seqOff[w] = d.textBase + seqOff;
+            if (d.format != kTextFasta && d.qualOff) d.qualOff[w] = d.textBase + qualOff;
+            d.rlen[w] = len; d.seeds[w] = seed;
+        }
     }
     // the block's sums: over the wavefront first, one set of atomics per wavefront
-    unsigned long long words = live ? (len + 31u) >> 5 : 0u, bases = live ? len : 0u;
-    uint32_t mx = live ? len : 0u;
+    unsigned long long words = kept ? (len + 31u) >> 5 : 0u, bases = kept ? len : 0u;
+    uint32_t mx = kept ? len : 0u;
     for (int m = CF_WAVE / 2; m > 0; m >>= 1) {
         words += cf_shfl_xor(words, m); bases += cf_shfl_xor(bases, m);
         const uint32_t o = cf_shfl_xor(mx, m); mx = o > mx ? o : mx;

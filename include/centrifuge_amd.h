@@ -408,6 +408,19 @@ int32_t   cf_text_column_of(const char *name);
  * (cf_last_error says which), and the slot keeps the program it had.  The program may change between batches; a change after a
  * batch's first cf_batch_wait_text does NOT format that batch again — its text is kept, and a second wait returns it as it is. */
 cf_status cf_batch_set_text_columns(cf_batch *, const int32_t *cols, uint32_t n_cols);
+/* -5 / -3 and -s for the slot's LATER cf_batch_upload_text, cf_batch_upload_bgzf and cf_batch_upload_bgzf_pair calls, until set
+ * again (the three share one record pass); a slot that never calls either uploads as before.
+ * Trim: a read is what is left of its record's bases without the first trim5 and the last trim3 of them, as the reference's parsers
+ * trim (pat.cpp) — lengths, seeds, the packed words and what cf_batch_wait_text prints (queryLength, readSeq*, readQual*) are the
+ * window's.  The plain form is still checked over the WHOLE record, trimmed letters and qualities included.  A record of which
+ * nothing is left makes the block `irregular` (CF_TEXT_EMPTY_SEQ): empty reads are the host parser's, with or without a trim.
+ * Skip: the first skip_reads records (pairs, with text2 / _pair) of each later upload are checked like the others and then dropped —
+ * BEFORE max_reads counts: the batch holds records skip_reads .. skip_reads + max_reads - 1.  skip_reads beyond the block's records
+ * is legal: n_reads == 0.  info->n_reads, n_bases and max_len report what is kept.  Where a BGZF text is cut and what comes back as
+ * its tail depend on neither. */
+#define CF_TEXT_EMPTY_SEQ 32u
+cf_status cf_batch_set_text_trim(cf_batch *, uint32_t trim5, uint32_t trim3);
+cf_status cf_batch_set_text_skip(cf_batch *, uint64_t skip_reads);
 
 /* pinned (page-locked) host memory: what makes the transfers of the async calls truly asynchronous */
 cf_status cf_host_alloc(void **p, size_t bytes);
