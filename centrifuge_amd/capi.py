@@ -82,7 +82,7 @@ class TextReads(C.Structure):
 
 class TextInfo(C.Structure):
     """cf_text_info of include/centrifuge_amd.h"""
-    _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("max_len", C.c_uint32), ("irregular", C.c_uint32)]
+    _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("max_len", C.c_uint32), ("irregular", C.c_uint32), ("paired", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class BgzfReads(C.Structure):
@@ -103,7 +103,7 @@ class ResultsText(C.Structure):
                 ("row_passes", C.c_uint32), ("slow_post", C.c_uint32), ("slow_score", C.c_uint32)]
 
 
-TEXT_FASTA, TEXT_FASTQ = 0, 1
+TEXT_FASTA, TEXT_FASTQ, TEXT_TAB5, TEXT_TAB6 = 0, 1, 2, 3           # (tabbed blocks: one read or both mates of a pair per line; TextInfo.paired says which)
 ROW16_DTYPE = np.dtype([("unique_id", "<u4"), ("taxon_idx", "<u4"), ("score", "<u4"), ("hit_len", "<u4")])
 RESULTS_ROWS, RESULTS_NARROW = 0, 1
 

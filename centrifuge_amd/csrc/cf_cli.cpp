@@ -48,6 +48,7 @@ static_assert(C_READ_ID == CF_COL_READ_ID && C_TAX_NAME == CF_COL_TAX_NAME && C_
 struct Opts {
     std::string index, outFile, reportFile = "centrifuge_report.tsv";
     std::vector<std::string> queries, mates1, mates2;
+    std::vector<std::string> tabs;                      // --tab5 / --12 / --tab6: files whose lines hold a read or both mates of a pair
     ReadFormat format = ReadFormat::Fastq;              // centrifuge.cpp:300 (FASTQ is the default)
     int khits = 5, minHitLen = 22, threads = 1, trim5 = 0, trim3 = 0, device = 0;
     int gpus = 1;                                       // --gpus N | all: devices device .. device+N-1, the index replicated on each
@@ -80,10 +81,15 @@ void usage(std::FILE *f) {
     std::fputs(
         "Centrifuge-compatible classifier, MI355X-native hot path (centrifuge_amd)\n"
         "Usage:\n"
-        "  centrifuge-class [options]* -x <cf-idx> {-1 <m1> -2 <m2> | -U <r>} [-S <filename>] [--report-file <report>]\n\n"
+        "  centrifuge-class [options]* -x <cf-idx> {-1 <m1> -2 <m2> | -U <r> | --tab5 <t> | --tab6 <t>} [-S <filename>] [--report-file <report>]\n\n"
         "  <cf-idx>   Index filename prefix (minus trailing .X.cf)\n"
         "  <m1>/<m2>  Files with #1 / #2 mates (comma-separated lists)\n"
         "  <r>        Files with unpaired reads (comma-separated list; '-' = stdin; .gz/.bz2 are piped)\n"
+        "  <t>        Tabbed files, one read or one pair per line (comma-separated list; '-' = stdin; .gz/.bz2 are piped):\n"
+        "             --tab5 / --12  name seq qual  or  name seq1 qual1 seq2 qual2;  --tab6  name1 seq1 qual1 name2 seq2 qual2\n"
+        "             A tabbed option switches the format of EVERY input of the run: -U / -1 / -2 files are then tabbed too, read one\n"
+        "             read per line (fields behind the third are ignored), so a file named by both --tab5 and -U is read twice.\n"
+        "             Plain and BGZF tabbed files take the device text path like FASTA / FASTQ files (see --host-io)\n"
         " Input:   -q (FASTQ, default)  -f (FASTA)  -r (one sequence per line)  -c (sequences on the command line)\n"
         "          -s/--skip <int>  -u/--upto <int>  -5/--trim5 <int>  -3/--trim3 <int>\n"
         " Classification:  -k <int> (5)  --min-hitlen <int> (22)  --host-taxids <t,..>  --exclude-taxids <t,..>\n"
@@ -151,6 +157,9 @@ Opts parse(int argc, const char **argv) {
         else if (a == "-U") { for (auto &s : splitComma(val())) o.queries.push_back(s); }
         else if (a == "-1") { for (auto &s : splitComma(val())) o.mates1.push_back(s); }
         else if (a == "-2") { for (auto &s : splitComma(val())) o.mates2.push_back(s); }
+        // the tabbed formats name their files and set the format for every input of the run (centrifuge.cpp:975-977)
+        else if (a == "--tab5" || a == "--12") { for (auto &s : splitComma(val())) o.tabs.push_back(s); o.format = ReadFormat::Tab5; }
+        else if (a == "--tab6") { for (auto &s : splitComma(val())) o.tabs.push_back(s); o.format = ReadFormat::Tab6; }
         else if (a == "-S" || a == "--output") o.outFile = val();
         else if (a == "--report-file") o.reportFile = val();
         else if (a == "-q") o.format = ReadFormat::Fastq;
@@ -209,7 +218,7 @@ Opts parse(int argc, const char **argv) {
         if (pi >= pos.size()) { usage(stderr); die("No index, query, or output file specified!"); }
         o.index = pos[pi++];
     }
-    const bool got = !o.queries.empty() || !o.mates1.empty();
+    const bool got = !o.queries.empty() || !o.mates1.empty() || !o.tabs.empty();        // centrifuge.cpp:3396
     if (pi >= pos.size()) { if (!got) { usage(stderr); die("***\nError: Must specify at least one read input with -U/-1/-2"); } }
     else if (!got) o.queries = splitComma(pos[pi++]);
     if (pi < pos.size() && o.outFile.empty()) {
@@ -399,6 +408,7 @@ struct GpuThread {
     uint64_t zMembers = 0;                          // BGZF members this thread had inflated on the device
     std::string zHead;                              // the text in front of the run in hand (the tail of the run before it)
     std::string zHead2;                             // ... of the second file of mates
+    std::string tabText;                            // a tabbed block parsed on the host: the text of its runs of pairs / unpaired reads, one behind the other
 };
 
 struct Runner {
@@ -714,6 +724,9 @@ struct Runner {
     // buffer, up as they are (cf_batch_upload_text: records, lengths, seeds and packed words are made on the device), the kernels,
     // and the default columns back as text (cf_batch_wait_text) — written at the block's own place in the output.  A block with a
     // record outside the plain form is parsed by the host parser instead (and its rows formatted here): same bytes out.
+    int32_t textFormatCode() const {
+        return o.format == ReadFormat::Fasta ? CF_TEXT_FASTA : o.format == ReadFormat::Tab5 ? CF_TEXT_TAB5 : o.format == ReadFormat::Tab6 ? CF_TEXT_TAB6 : CF_TEXT_FASTQ;
+    }
     void classifyText(Batch &b, GpuThread &g, size_t gi) {
         auto t0 = std::chrono::steady_clock::now();
         auto lap = [&](double &acc) { const auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(t - t0).count(); t0 = t; };
@@ -732,22 +745,29 @@ struct Runner {
         if (mates) readFileRange(b.tFd2, g.tin + at2, (size_t)b.tLen2, b.tOff2, *b.tPath2);
         lap(g.tm.read);
         const bool fasta = o.format == ReadFormat::Fasta;
+        const bool tab = o.format == ReadFormat::Tab5 || o.format == ReadFormat::Tab6;
         CF_TRY(cf_batch_set_result_format(g.slot, CF_RESULTS_NARROW));
         cf_text_reads in{};
-        in.text = g.tin; in.n_bytes = b.tLen; in.format = fasta ? CF_TEXT_FASTA : CF_TEXT_FASTQ; in.global_seed = o.seed; in.max_reads = 0;
+        in.text = g.tin; in.n_bytes = b.tLen; in.format = textFormatCode(); in.global_seed = o.seed; in.max_reads = 0;
         if (mates) { in.text2 = g.tin + at2; in.n_bytes2 = b.tLen2; }
-        const uint64_t per = mates ? 2 : 1;
+        uint64_t per = mates ? 2 : 1;
         cf_text_info info{};
         const bool tryDevice = !(cfamd::cf_knob("CF_CLI_TEXT_HOST_PARSE") && std::atoi(cfamd::cf_knob("CF_CLI_TEXT_HOST_PARSE")));   // (the tests: every block through the fallback)
         if (tryDevice) CF_TRY(cf_batch_upload_text(g.slot, &in, g.stream, &info)); else info.irregular = 1;
         lap(g.tm.parse);
         bool onHost = info.irregular != 0;
+        if (info.paired) per = 2;                                       // (a tabbed block of pair lines)
         uint64_t nReads = info.n_reads / per;                           // queries: reads, or pairs
         if (onHost) {
             // the host parser's semantics are the reference's for every record: this block alone pays for what it holds
             b.r.clear(); b.r.hasQual = false;
             try {
                 if (fasta) parseFastaChunk(g.tin, g.tin + b.tLen, b.tFirst, o.trim5, o.trim3, o.seed, b.r, b.tLast);
+                else if (tab) {
+                    parseTabChunk(g.tin, g.tin + b.tLen, o.format == ReadFormat::Tab6, true, o.trim5, o.trim3, o.seed, b.r, b.tLast);
+                    // (the reference stops reading a file at a name with a line end in it; the blocks behind this one are on their way)
+                    if (b.r.inputEnded && !b.tLast) throw std::runtime_error("Error: reads file does not look like a tabbed file: a line without a tab near byte " + std::to_string(b.tOff) + " of " + *b.tPath + "; run with --host-io to read it up to there");
+                }
                 else parseFastqChunk(g.tin, g.tin + b.tLen, b.tFirst, o.trim5, o.trim3, o.seed, b.r, b.tLast);
                 if (mates) {
                     b.r2.clear(); b.r2.hasQual = false;
@@ -762,6 +782,7 @@ struct Runner {
                 die(msg);
             }
             nReads = b.r.size();
+            if (tab) { nReads = 0; for (uint8_t m : b.r.mate) nReads += m != 2; }        // (records: a pair line is one)
             if (mates) {
                 // (the two blocks were cut to hold the same records; at the end of the files one may hold fewer: the messages of the other path)
                 if (b.r2.size() != nReads && !b.tLast)
@@ -803,7 +824,9 @@ struct Runner {
             lap(g.tm.report);
         } else {
             g.hostBlocks++;
-            if (mates || take < nReads || b.r.hasEmptyName()) {
+            ReadSoA tabSrc;
+            if (tab) std::swap(tabSrc, b.r);
+            else if (mates || take < nReads || b.r.hasEmptyName()) {
                 // reads in front of -s and past -u go, reads without a name are named after their ordinal, mates are laid side by side: the block's records one by one
                 ReadSoA src;
                 std::swap(src, b.r);
@@ -817,6 +840,8 @@ struct Runner {
                 };
                 for (uint64_t i = drop; i < drop + take; i++) { one(src, i); if (mates) one(b.r2, i); }
             }
+            // the reads of b.r through the kernels and the host formatter: their text into this thread's buffer
+            auto hostRun = [&](bool mates) {
             b.r.pack();
             b.paired = mates;
             const PackedSoA &pk = b.r.pk;
@@ -862,8 +887,31 @@ struct Runner {
                 std::memcpy(ob.room(s.size()), s.data(), s.size());
                 ob.len = s.size();
             }
-            text = ob.p.get(); nText = ob.len;
             lap(g.tm.format);
+            };
+            if (!tab) { hostRun(mates); text = hostOut[gi]->p.get(); nText = hostOut[gi]->len; }
+            else {
+                // a tabbed block: its records [drop, drop + take) in runs of one kind — pair lines or three-field lines —, a run a
+                // batch; a record without a name is named after its number (both mates alike)
+                g.tabText.clear();
+                uint64_t rec = 0;
+                for (size_t i = 0; i < tabSrc.size();) {
+                    const bool pr = tabSrc.mate[i] == 1;
+                    b.r.clear(); b.r.hasQual = false;
+                    for (; i < tabSrc.size() && (tabSrc.mate[i] == 1) == pr; i += pr ? 2 : 1, rec++) {
+                        if (rec < drop || rec >= drop + take) continue;
+                        for (size_t k = i; k < i + (pr ? 2 : 1); k++) {
+                            if (tabSrc.nameOff[k + 1] > tabSrc.nameOff[k]) { b.r.appendRecord(tabSrc, k); continue; }
+                            const std::string nm = std::to_string(base + rec);
+                            const uint64_t len = tabSrc.off[k + 1] - tabSrc.off[k];
+                            const uint8_t *q = tabSrc.qual.data() + tabSrc.off[k];
+                            b.r.push(tabSrc.seq.data() + tabSrc.off[k], q, len, nm.data(), nm.size(), cf_gen_rand_seed(tabSrc.seq.data() + tabSrc.off[k], q, len, nm.data(), nm.size(), o.seed));
+                        }
+                    }
+                    if (b.r.size()) { hostRun(pr); g.tabText.append(hostOut[gi]->p.get(), hostOut[gi]->len); }
+                }
+                text = g.tabText.data(); nText = g.tabText.size();
+            }
         }
         // the block's place in the output: behind the blocks before it
         const uint64_t at = outChain.enter(b.tIdx);
@@ -893,7 +941,7 @@ struct Runner {
         lap(g.tm.read);
         CF_TRY(cf_batch_set_result_format(g.slot, CF_RESULTS_NARROW));
         cf_bgzf_reads in{};
-        in.members = g.tin; in.n_bytes = b.tLen; in.format = o.format == ReadFormat::Fasta ? CF_TEXT_FASTA : CF_TEXT_FASTQ;
+        in.members = g.tin; in.n_bytes = b.tLen; in.format = textFormatCode();
         in.global_seed = o.seed; in.max_reads = 0; in.last = b.tLast ? 1 : 0;
         cf_text_info info{};
         cf_bgzf_info zi{};
@@ -913,7 +961,8 @@ struct Runner {
         }
         tailChain.leave(0);
         lap(g.tm.parse);
-        const uint64_t nReads = skip ? 0 : info.n_reads;
+        const uint64_t per = info.paired ? 2 : 1;                       // (a tabbed run of pair lines: -s / -u count records)
+        const uint64_t nReads = skip ? 0 : info.n_reads / per;
         const uint64_t base = readChain.enter(b.tIdx);
         readChain.leave(nReads);
         const uint64_t drop = base >= o.skip ? 0 : std::min<uint64_t>(nReads, o.skip - base);     // (-s / -u: as in classifyText)
@@ -928,7 +977,7 @@ struct Runner {
                 CF_TRY(cf_batch_set_text_skip(g.slot, drop));
                 CF_TRY(cf_batch_upload_bgzf(g.slot, &in, g.stream, &info, &zi));
                 CF_TRY(cf_batch_set_text_skip(g.slot, 0));
-                if (info.irregular || zi.corrupt || info.n_reads != take) die("internal error: a run of members changed between two uploads");
+                if (info.irregular || zi.corrupt || info.n_reads != take * per) die("internal error: a run of members changed between two uploads");
             }
             CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
             lap(g.tm.create);
@@ -1186,8 +1235,15 @@ int run(int argc, const char **argv) {
     Runner R{o};
     // The reference works through its inputs one at a time, mate files first (centrifuge.cpp:3007-3040): read
     // ordinals, -s/-u and the names of unnamed reads start over with every input.
-    struct Input { std::string f1, f2; bool paired; };
+    // Tabbed files come first: PairedPatternSource::setupPatternSources makes the sources of --12 / --tab5 / --tab6 files in front of
+    // those of -1 / -2 and of the unpaired files (pat.cpp:349-362, then 382-413, then 418-436).  The reference binary itself reads
+    // none of them: its loop over the inputs (centrifuge.cpp:3007-3060) counts and hands over -1 / -2 and -U files only, so there
+    // a tabbed option does nothing but switch those files' format — they are then read a line a read (TabbedPatternSource::read),
+    // as they are here — and a run with --tab5 alone prints the header.  Here the files are read, by TabbedPatternSource::readPair's
+    // rules (cf_ingest.cpp parseTabChunk).
+    struct Input { std::string f1, f2; bool paired; bool tab = false; };
     std::vector<Input> inputs;
+    for (const auto &t : o.tabs) inputs.push_back({t, std::string(), false, true});
     for (size_t i = 0; i < o.mates1.size(); i++) inputs.push_back({o.mates1[i], o.mates2[i], true});
     for (const auto &q : o.queries) inputs.push_back({q, std::string(), false});
     if (!o.dumpReads) {
@@ -1210,7 +1266,7 @@ int run(int argc, const char **argv) {
         if (o.expectedReads >= 0) expected = (uint64_t)o.expectedReads;
         else if (o.format == ReadFormat::CmdLine) expected = 1 + o.queries.size() + 2 * o.mates1.size();
         else {
-            const double perRead = o.format == ReadFormat::Fastq ? 100.0 : o.format == ReadFormat::Fasta ? 60.0 : 30.0;
+            const double perRead = o.format == ReadFormat::Fastq || o.format == ReadFormat::Tab5 || o.format == ReadFormat::Tab6 ? 100.0 : o.format == ReadFormat::Fasta ? 60.0 : 30.0;
             double reads = 0;
             bool unknown = false;
             auto add = [&](const std::string &f) {
@@ -1280,7 +1336,7 @@ int run(int argc, const char **argv) {
         // The device text path (round 6): whole blocks of a plain FASTA / FASTQ file up as text, the rows back as text — with
         // -5 / -3 as the record pass's window (cf_batch_set_text_trim), -s / -u by the block (cf_batch_set_text_skip, max_reads), up to CF_TEXT_MAX_COLS columns (cf_batch_set_text_columns), -k <= 63 (the narrow rows' six bits).  Every GPU thread
         // then also reads its blocks and writes its text, so there are more of them (each with a slot on the device).
-        R.textCapable = !ordered && o.cols.size() <= CF_TEXT_MAX_COLS && (o.format == ReadFormat::Fasta || o.format == ReadFormat::Fastq) &&
+        R.textCapable = !ordered && o.cols.size() <= CF_TEXT_MAX_COLS && (o.format == ReadFormat::Fasta || o.format == ReadFormat::Fastq || o.format == ReadFormat::Tab5 || o.format == ReadFormat::Tab6) &&
                         o.khits <= 63 && !o.hostIo &&
                         !(cfamd::cf_knob("CF_CLI_DEVICE_TEXT") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_TEXT")));
         const int slots = ordered ? 1 : (R.textCapable && !o.slotsSet) ? std::max(2, std::min(6, o.threads / 2)) : o.slots;
@@ -1412,7 +1468,8 @@ int run(int argc, const char **argv) {
         struct stat isb;
         uint64_t resume1 = 0, resume2 = 0, resumeId = 0;              // where the parser pool takes over from the text path (mates, BGZF files)
         std::string resumeHead, resumeHead2;                          // ... a BGZF file: the text in front of the member at resume1 (resume2)
-        if (R.textCapable && paired && !o.dumpReads && in.f1 != "-" && in.f2 != "-" && ::stat(in.f1.c_str(), &isb) == 0 && S_ISREG(isb.st_mode) &&
+        const bool tabRun = o.format == ReadFormat::Tab5 || o.format == ReadFormat::Tab6;      // (text path: the files a tabbed option names; -U / -1 / -2 files of such a run are read a line a read, on the host)
+        if (R.textCapable && !tabRun && paired && !o.dumpReads && in.f1 != "-" && in.f2 != "-" && ::stat(in.f1.c_str(), &isb) == 0 && S_ISREG(isb.st_mode) &&
             ::stat(in.f2.c_str(), &isb) == 0 && S_ISREG(isb.st_mode)) {
             // Mates on the device text path: the first file is cut like an unpaired one; the second where it holds as many records
             // as the first file's block — counted here, 32 bytes at a time over mappings of the two files, by the rule the device's
@@ -1569,7 +1626,7 @@ int run(int argc, const char **argv) {
                 for (uint64_t at = resume2; at < zs2 && bgzfMemberAt(zp[1], zs2, at, bs, is); at += bs) zHostMembers++;
             }
         }
-        if (R.textCapable && !paired && !o.dumpReads && in.f1 != "-" && ::stat(in.f1.c_str(), &isb) == 0 && S_ISREG(isb.st_mode)) {
+        if (R.textCapable && (!tabRun || in.tab) && !paired && !o.dumpReads && in.f1 != "-" && ::stat(in.f1.c_str(), &isb) == 0 && S_ISREG(isb.st_mode)) {
             // The device text path: a plain file (not stdin, a pipe or a compressed one) is dealt out to the GPU threads as ranges
             // that start and end at record starts; each reads its range, sends it up as it is and writes the text that comes back.
             ByteSource src(in.f1, 1);                             // (throws when the file cannot be opened, as the other path does)
@@ -1589,7 +1646,7 @@ int run(int argc, const char **argv) {
                 uint64_t pos = 0, idx = 0;
                 while (pos < fsize && !R.uptoReached) {
                     const auto tp0 = std::chrono::steady_clock::now();
-                    const uint64_t cut = nextRecordCut(fd, pos, fsize, kBlock, o.format == ReadFormat::Fasta, in.f1);
+                    const uint64_t cut = nextRecordCut(fd, pos, fsize, kBlock, o.format == ReadFormat::Fasta, in.f1, tabRun);
                     std::unique_ptr<Batch> b;
                     { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
                     if (!b) b = std::make_unique<Batch>();
@@ -1672,9 +1729,10 @@ int run(int argc, const char **argv) {
         // the knob CF_DUMP_FROM_PACKED=1 prints the bases back out of the packed form — the tests' window on it.)
         const bool dumpPacked = o.dumpReads && cfamd::cf_knob("CF_DUMP_FROM_PACKED") && std::atoi(cfamd::cf_knob("CF_DUMP_FROM_PACKED"));
         const bool wantPacked = o.dumpReads ? dumpPacked : !(cfamd::cf_knob("CF_CLI_PACKED") && !std::atoi(cfamd::cf_knob("CF_CLI_PACKED")));
-        ChunkedReader s1({in.f1}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume1, resumeHead);
+        const bool tabFmt = o.format == ReadFormat::Tab5 || o.format == ReadFormat::Tab6;
+        ChunkedReader s1({in.f1}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked && !in.tab, resume1, resumeHead, in.tab);
         std::unique_ptr<ChunkedReader> s2;
-        if (paired) s2.reset(new ChunkedReader({in.f2}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume2, resumeHead2));
+        if (paired) s2.reset(new ChunkedReader({in.f2}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked, resume2, resumeHead2, false));
         ReadSoA c1, c2;
         size_t i1 = 0, i2 = 0;
         bool c1Named = false, c2Named = false; // the current chunk of the stream has no unnamed read (bulk path allowed)
@@ -1700,6 +1758,85 @@ int run(int argc, const char **argv) {
         uint64_t rdid = resumeId;
         uint64_t dumpWordAt = 0, dumpNAt = 0, dumpBatches = 0, dumpFromPacked = 0;
         bool more = true;
+        // an assembled batch: counted (--ingest-bench), printed (--dump-reads) or handed to the GPU threads; false: the run is failing
+        auto finish = [&](std::unique_ptr<Batch> b, std::chrono::steady_clock::time_point tp0) -> bool {
+            if (o.ingestBench) {                     // count, and hand the batch's arrays back as the pipeline's last stage would
+                benchReads += b->r.size(); benchBases += b->r.seq.size();
+                std::lock_guard<std::mutex> lk(mu); spare.push_back(std::move(b));
+                return true;
+            }
+            if (o.dumpReads) {
+                if (dumpPacked) { dumpBatches++; if (b->r.pk.valid) dumpFromPacked++; }
+                for (size_t i = 0; i < b->r.size(); i++) {
+                    std::string ln(b->r.names.data() + b->r.nameOff[i], b->r.nameOff[i + 1] - b->r.nameOff[i]);
+                    ln.push_back('\t');
+                    if (dumpPacked && b->r.pk.valid) {            // the bases as the packed form holds them
+                        const PackedSoA &pk = b->r.pk;
+                        if (i == 0) { dumpWordAt = 0; dumpNAt = 0; }
+                        const uint32_t L = pk.lens.p[i];
+                        for (uint32_t j = 0; j < L; j++) {
+                            const uint64_t wi = dumpWordAt + (j >> 5);
+                            while (dumpNAt < pk.nN && pk.nIdx.p[dumpNAt] < wi) dumpNAt++;
+                            const bool isN = dumpNAt < pk.nN && pk.nIdx.p[dumpNAt] == wi && ((pk.nMsk.p[dumpNAt] >> (j & 31)) & 1u);
+                            ln.push_back(isN ? 'N' : "ACGT"[(pk.words.p[wi] >> (2 * (j & 31))) & 3]);
+                        }
+                        dumpWordAt += (L + 31) >> 5;
+                        if (pk.seeds.p[i] != b->r.seeds[i] || pk.nReads != b->r.size()) die("internal error: packed form out of step");
+                    } else appendSeq(ln, b->r, i);
+                    ln.push_back('\t'); appendQual(ln, b->r, i);
+                    ln += "\t" + std::to_string(b->r.seeds[i]) + "\n";
+                    std::fwrite(ln.data(), 1, ln.size(), stdout);
+                }
+                return true;
+            }
+            lastSeq = std::max(lastSeq, b->r.seq.size()); lastNames = std::max(lastNames, b->r.names.size());
+            lastReads = std::max(lastReads, b->r.size()); lastQual = lastQual || b->r.hasQual;
+            const auto tp1 = std::chrono::steady_clock::now();
+            R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
+            if (!submit(std::move(b))) { aborted = true; return false; }
+            R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+            return true;
+        };
+        if (tabFmt && !paired) {
+            // A tabbed file: a line is a record — one read, or (in.tab) both mates of a pair.  -s / -u count records, a record without a
+            // name is named after its number (both mates of a pair alike), and a batch holds pairs only or unpaired reads only: it
+            // is closed where the kind of line changes, so a file that mixes them is classified and printed in file order.
+            ReadSoA c;
+            std::unique_ptr<Batch> b;
+            auto tp0 = std::chrono::steady_clock::now();
+            bool ok = true, upto = false;
+            auto close = [&]() { if (b && b->r.size()) ok = finish(std::move(b), tp0); b.reset(); tp0 = std::chrono::steady_clock::now(); };
+            while (ok && !upto && s1.next(c)) {
+                if (c.mate.size() != c.size()) die("internal error: a tabbed chunk without its mate flags");
+                const bool named = !c.hasEmptyName();
+                for (size_t i = 0; i < c.size() && ok;) {
+                    const bool pr = c.mate[i] == 1;
+                    const size_t per = pr ? 2 : 1;
+                    if (rdid >= o.upto) { upto = true; break; }
+                    if (b && b->r.size() && (b->paired != pr || b->r.size() >= o.batch * per)) close();
+                    if (!ok) break;
+                    if (!b) {
+                        { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
+                        if (!b) b = std::make_unique<Batch>();
+                        b->r.clear(); b->r.hasQual = false; b->nq = 0; b->endOfInput = -1; b->isText = false; b->narrowRows = false;
+                        b->paired = pr;
+                    }
+                    // as many records of the same kind as follow, fit the batch and lie inside the -s / -u window: in one piece
+                    size_t j = i;
+                    if (named && rdid >= o.skip) {
+                        const uint64_t room = std::min<uint64_t>(o.batch - b->r.size() / per, o.upto - rdid);
+                        while (j < c.size() && (c.mate[j] == 1) == pr && (j - i) / per < room) j += per;
+                    }
+                    if (j > i) { b->r.appendRange(c, i, j); rdid += (j - i) / per; i = j; continue; }
+                    const uint64_t id = rdid++;
+                    if (id >= o.skip) { take(*b, c, i, id); if (pr) take(*b, c, i + 1, id); }
+                    i += per;
+                }
+            }
+            if (ok) close();
+            if (!ok) aborted = true;
+            more = false;
+        }
         while (more) {
             const auto tp0 = std::chrono::steady_clock::now();
             std::unique_ptr<Batch> b;
@@ -1756,41 +1893,7 @@ int run(int argc, const char **argv) {
                 }
                 i1++; i2++;
             }
-            if (o.ingestBench) {                     // count, and hand the batch's arrays back as the pipeline's last stage would
-                benchReads += b->r.size(); benchBases += b->r.seq.size();
-                std::lock_guard<std::mutex> lk(mu); spare.push_back(std::move(b));
-                continue;
-            }
-            if (o.dumpReads) {
-                if (dumpPacked) { dumpBatches++; if (b->r.pk.valid) dumpFromPacked++; }
-                for (size_t i = 0; i < b->r.size(); i++) {
-                    std::string ln(b->r.names.data() + b->r.nameOff[i], b->r.nameOff[i + 1] - b->r.nameOff[i]);
-                    ln.push_back('\t');
-                    if (dumpPacked && b->r.pk.valid) {            // the bases as the packed form holds them
-                        const PackedSoA &pk = b->r.pk;
-                        if (i == 0) { dumpWordAt = 0; dumpNAt = 0; }
-                        const uint32_t L = pk.lens.p[i];
-                        for (uint32_t j = 0; j < L; j++) {
-                            const uint64_t wi = dumpWordAt + (j >> 5);
-                            while (dumpNAt < pk.nN && pk.nIdx.p[dumpNAt] < wi) dumpNAt++;
-                            const bool isN = dumpNAt < pk.nN && pk.nIdx.p[dumpNAt] == wi && ((pk.nMsk.p[dumpNAt] >> (j & 31)) & 1u);
-                            ln.push_back(isN ? 'N' : "ACGT"[(pk.words.p[wi] >> (2 * (j & 31))) & 3]);
-                        }
-                        dumpWordAt += (L + 31) >> 5;
-                        if (pk.seeds.p[i] != b->r.seeds[i] || pk.nReads != b->r.size()) die("internal error: packed form out of step");
-                    } else appendSeq(ln, b->r, i);
-                    ln.push_back('\t'); appendQual(ln, b->r, i);
-                    ln += "\t" + std::to_string(b->r.seeds[i]) + "\n";
-                    std::fwrite(ln.data(), 1, ln.size(), stdout);
-                }
-                continue;
-            }
-            lastSeq = std::max(lastSeq, b->r.seq.size()); lastNames = std::max(lastNames, b->r.names.size());
-            lastReads = std::max(lastReads, b->r.size()); lastQual = lastQual || b->r.hasQual;
-            const auto tp1 = std::chrono::steady_clock::now();
-            R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
-            if (!submit(std::move(b))) { aborted = true; break; }
-            R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+            if (!finish(std::move(b), tp0)) break;
         }
         if (dumpPacked) std::fprintf(stderr, "dumped from the packed form: %llu of %llu batches\n", (unsigned long long)dumpFromPacked, (unsigned long long)dumpBatches);
         if (o.separator && !o.dumpReads && !aborted) {          // marker behind the input's last batch (centrifuge.cpp:3128-3226)

@@ -276,7 +276,9 @@ __global__ void __launch_bounds__(256) k_compact(DCompact c) {
 // the text forms (cf_textio.hpp): ingest and egress of the front end on the device, one thread per piece / record / query
 __global__ void __launch_bounds__(256) k_text_count(DTextMark m) { text_count_body(m, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(256) k_text_mark(DTextMark m) { text_mark_body(m, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
-__global__ void __launch_bounds__(256) k_text_records(DTextRec d) { text_record_body(d, cf_global_thread()); }
+__global__ void __launch_bounds__(256) k_text_records(DTextRec d) { text_record_body_t<false>(d, cf_global_thread()); }
+// (the tabbed formats: an instantiation of their own, so that the FASTA / FASTQ pass keeps its registers)
+__global__ void __launch_bounds__(256) k_text_records_tab(DTextRec d) { text_record_body_t<true>(d, cf_global_thread()); }
 // BGZF members inflated on the device (cf_inflate.hpp): a wavefront per member, its tables in LDS (4 x 3.9 KiB per block); the
 // one-lane-per-member form — tables in the lane's scratch memory — is kept for the comparison of the two (CF_INFLATE_LANES=1)
 __global__ void __launch_bounds__(256) k_inflate(DInflate d) {
@@ -1989,7 +1991,9 @@ static void uploadDense(cf_batch *bt, const cf_dense_reads *in, hipStream_t st) 
 // lengths, seeds and places per record (cf_textio.hpp) — and ONE wait for the status: the number of reads sizes the slot.  A block
 // that is not in the plain form leaves the slot without a batch (info->irregular says why): the caller's host parser takes it.
 static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf_text_info *info) {
-    if (in->format != CF_TEXT_FASTA && in->format != CF_TEXT_FASTQ) throw ArgError("cf_text_reads::format is CF_TEXT_FASTA or CF_TEXT_FASTQ");
+    if (in->format < CF_TEXT_FASTA || in->format > CF_TEXT_TAB6) throw ArgError("cf_text_reads::format is CF_TEXT_FASTA, CF_TEXT_FASTQ, CF_TEXT_TAB5 or CF_TEXT_TAB6");
+    const bool tab = in->format >= CF_TEXT_TAB5;
+    if (tab && in->text2) throw ArgError("a tabbed block holds both mates: cf_text_reads::text2 must be NULL");
     const int nBlocks = in->text2 ? 2 : 1;
     const char *src[2] = {in->text, in->text2};
     const uint64_t nBs[2] = {in->n_bytes, in->text2 ? in->n_bytes2 : 0};
@@ -2006,7 +2010,7 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
         textBytes += pieces[k] * kTextPiece + kTextPad; nPieces += pieces[k] + 16; posTotal += posCap[k] + 16;
         recMax = std::max(recMax, recCap[k]);
     }
-    const uint64_t readCap = recMax * (uint64_t)nBlocks;
+    const uint64_t readCap = recMax * (uint64_t)(tab ? 2 : nBlocks);            // (a tabbed record may be a pair)
     bt->text.ensure(textBytes);
     bt->txCnt.ensure(nPieces + 16); bt->txBase.ensure(nPieces + 16); bt->txPos.ensure(posTotal + 16);
     bt->txTileA.ensure(scan_tiles_for(std::max(pieces[0], pieces[nBlocks - 1])) + 1); bt->txTileC.ensure(scan_tiles_for(std::max(pieces[0], pieces[nBlocks - 1])) + 1);
@@ -2033,27 +2037,29 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
         DTextRec d{text, nBs[k], pos, base + pieces[k], posCap[k], (uint32_t)recCap[k], (uint32_t)in->format, seed0,
                    bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], (uint32_t)nBlocks, (uint32_t)k,
                    fasta ? nullptr : bt->txQualOff.p, bt->textTrim5, bt->textTrim3, bt->textSkip};
-        hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
+        if (tab) hipLaunchKernelGGL(k_text_records_tab, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
+        else hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
         HIP_OK(hipMemcpyAsync(bt->hTxTotal.p + k, base + pieces[k], 8, hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
-    const TextStatus ts = *bt->hTxSt.p;
+    TextStatus ts = *bt->hTxSt.p;
+    const bool tabPairs = tab && text_tab_kind(ts.flags);
     uint64_t nRec[2] = {0, 0};
-    for (int k = 0; k < nBlocks; k++) nRec[k] = fasta ? bt->hTxTotal.p[k] : bt->hTxTotal.p[k] >> 2;
+    for (int k = 0; k < nBlocks; k++) nRec[k] = fasta || tab ? bt->hTxTotal.p[k] : bt->hTxTotal.p[k] >> 2;
     if (ts.flags) { info->irregular = ts.flags; return; }
     if (nBlocks == 2 && nRec[0] != nRec[1]) { info->irregular = kTxMateCount; return; }
     uint64_t nq = nRec[0] - std::min<uint64_t>(nRec[0], bt->textSkip);  // (cf_batch_set_text_skip: dropped before max_reads counts)
     if (in->max_reads && nq > in->max_reads) nq = in->max_reads;     // (the sums below then cover a few reads too many: upper bounds, as they may be)
-    const uint64_t nReads = nq * (uint64_t)nBlocks;
-    sizeBatch(bt, nReads, ts.words(), ts.bases(), ts.maxLen, nBlocks == 2);
+    const uint64_t nReads = nq * (uint64_t)(tabPairs ? 2 : nBlocks);
+    sizeBatch(bt, nReads, ts.words(), ts.bases(), ts.maxLen, nBlocks == 2 || tabPairs);
     bindBatch(bt);
     HIP_OK(hipEventRecord(bt->ev[8], st));
     bt->fromText = true; bt->fromBytes = false; bt->densePending = 0; bt->revMade = false; bt->nmaskZeroOf = nullptr;   // (k_text_pack writes every mask word)
     bt->textFastq = !fasta;
     bt->loaded = true;
-    info->n_reads = nReads; info->n_bases = ts.bases(); info->max_len = ts.maxLen;
+    info->n_reads = nReads; info->n_bases = ts.bases(); info->max_len = ts.maxLen; info->paired = nBlocks == 2 || tabPairs ? 1u : 0u;
 }
 
 // BGZF members (cf_bgzf_reads): the compressed bytes up, inflated on the device into the slot's text buffer behind the head the
@@ -2062,7 +2068,8 @@ static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf
 // status and the cut (the record pass is launched with them), and for the parse.
 constexpr uint64_t kBgzfTailRoom = 1u << 20;
 static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf_text_info *info, cf_bgzf_info *zi) {
-    if (in->format != CF_TEXT_FASTA && in->format != CF_TEXT_FASTQ) throw ArgError("cf_bgzf_reads::format is CF_TEXT_FASTA or CF_TEXT_FASTQ");
+    if (in->format < CF_TEXT_FASTA || in->format > CF_TEXT_TAB6) throw ArgError("cf_bgzf_reads::format is CF_TEXT_FASTA, CF_TEXT_FASTQ, CF_TEXT_TAB5 or CF_TEXT_TAB6");
+    const bool tab = in->format >= CF_TEXT_TAB5;
     if ((in->n_bytes && !in->members) || (in->head_bytes && !in->head)) throw ArgError("null member / head bytes");
     if (in->n_bytes >= 0xffff0000ull || in->head_bytes >= 0xffff0000ull) throw ArgError("the text of a batch holds fewer than 2^32 - 65536 bytes (32-bit places in it)");
     *info = cf_text_info{}; *zi = cf_bgzf_info{};
@@ -2098,9 +2105,10 @@ static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf
     bt->hZCut.ensure(4); bt->hTail.ensure(kBgzfTailRoom + 16);
     bt->txCnt.ensure(pieces + 32); bt->txBase.ensure(pieces + 32); bt->txPos.ensure(posCap + 32);
     bt->txTileA.ensure(scan_tiles_for(pieces) + 1); bt->txTileC.ensure(scan_tiles_for(pieces) + 1);
-    bt->rlen.ensure(recCap + 16); bt->seeds.ensure(recCap + 16);
-    bt->txSeqOff.ensure(recCap + 16); bt->txIdOff.ensure(recCap + 16); bt->txIdLen.ensure(recCap + 16);
-    if (!fasta) bt->txQualOff.ensure(recCap + 16);
+    const uint64_t readCap = tab ? 2 * recCap : recCap;                          // (a tabbed record may be a pair)
+    bt->rlen.ensure(readCap + 16); bt->seeds.ensure(readCap + 16);
+    bt->txSeqOff.ensure(readCap + 16); bt->txIdOff.ensure(readCap + 16); bt->txIdLen.ensure(readCap + 16);
+    if (!fasta) bt->txQualOff.ensure(readCap + 16);
     bt->txSt.ensure(1); bt->hTxSt.ensure(1); bt->hTxTotal.ensure(2);
     HIP_OK(hipMemsetAsync(bt->txSt.p, 0, sizeof(TextStatus), st));
     HIP_OK(hipMemsetAsync(bt->zSt.p, 0, sizeof(InfStatus), st));
@@ -2121,7 +2129,7 @@ static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf
     if (pieces) hipLaunchKernelGGL(k_text_count, gp, bl, 0, st, mk);
     scan_enqueue<SCAN_PLAIN>(bt->txCnt.p, pieces, bt->txBase.p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
     if (pieces) hipLaunchKernelGGL(k_text_mark, gp, bl, 0, st, mk);
-    const DTextCut ct{text, total, bt->txPos.p, bt->txBase.p + pieces, posCap, fasta ? 0u : 1u, in->last ? 1u : 0u, bt->zCut.p};
+    const DTextCut ct{text, total, bt->txPos.p, bt->txBase.p + pieces, posCap, fasta ? 0u : tab ? 2u : 1u, in->last ? 1u : 0u, bt->zCut.p};
     hipLaunchKernelGGL(k_text_cut, dim3(1), dim3(64), 0, st, ct);
     HIP_OK(hipMemcpyAsync(bt->hZCut.p, bt->zCut.p, 16, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(bt->hZCut.p + 2, bt->zSt.p, sizeof(InfStatus), hipMemcpyDeviceToHost, st));
@@ -2142,22 +2150,24 @@ static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf
     const DTextRec d{text, cut, bt->txPos.p, bt->zCut.p + 1, posCap, (uint32_t)recCap, (uint32_t)in->format, seed0,
                      bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, 0u, 1u, 0u, fasta ? nullptr : bt->txQualOff.p,
                      bt->textTrim5, bt->textTrim3, bt->textSkip};
-    hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap + 255) / 256)), bl, 0, st, d);
+    if (tab) hipLaunchKernelGGL(k_text_records_tab, dim3((unsigned)((recCap + 255) / 256)), bl, 0, st, d);
+    else hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap + 255) / 256)), bl, 0, st, d);
     HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
-    const TextStatus ts = *bt->hTxSt.p;
+    TextStatus ts = *bt->hTxSt.p;
+    const bool tabPairs = tab && text_tab_kind(ts.flags);
     if (ts.flags) { info->irregular = ts.flags; return; }
-    uint64_t nq = fasta ? bt->hZCut.p[1] : bt->hZCut.p[1] >> 2;
+    uint64_t nq = fasta || tab ? bt->hZCut.p[1] : bt->hZCut.p[1] >> 2;
     nq -= std::min<uint64_t>(nq, bt->textSkip);
     if (in->max_reads && nq > in->max_reads) nq = in->max_reads;
-    sizeBatch(bt, nq, ts.words(), ts.bases(), ts.maxLen, false);
+    sizeBatch(bt, tabPairs ? 2 * nq : nq, ts.words(), ts.bases(), ts.maxLen, tabPairs);
     bindBatch(bt);
     HIP_OK(hipEventRecord(bt->ev[8], st));
     bt->fromText = true; bt->fromBytes = false; bt->densePending = 0; bt->revMade = false; bt->nmaskZeroOf = nullptr;
     bt->textFastq = !fasta;
     bt->loaded = true;
-    info->n_reads = nq; info->n_bases = ts.bases(); info->max_len = ts.maxLen;
+    info->n_reads = tabPairs ? 2 * nq : nq; info->n_bases = ts.bases(); info->max_len = ts.maxLen; info->paired = tabPairs ? 1u : 0u;
     zi->tail = reinterpret_cast<const char *>(bt->hTail.p); zi->tail_bytes = total - cut;
 }
 

@@ -316,6 +316,7 @@ CF_DEV void inflate_body(const DInflate &d, uint32_t m, uint32_t lane, InfTables
 // and format passes of cf_textio.hpp), what lies behind it is the next upload's head.  Purely syntactic:
 //   FASTQ  behind the last '\n' whose count from the text's start is a multiple of 4
 //   FASTA  in front of the last '>' that starts the text or follows a '\n'
+//   TAB5 / TAB6 (fastq == 2)  behind the last '\n'; with `last` a text that does not end in '\n' is irregular (the record pass says so)
 // `last` (no member follows): the text's end.  One thread; pos / total are the marker pass's ('>' or '\n' places, their number).
 struct DTextCut {
     const uint8_t *text;
@@ -323,7 +324,7 @@ struct DTextCut {
     const uint32_t *pos;
     const uint64_t *total;
     uint64_t posCap;
-    uint32_t fastq, last;
+    uint32_t fastq, last;        // fastq: 0 FASTA, 1 FASTQ, 2 a record a line (the tabbed formats)
     uint64_t *cut;               // [0] the cut, [1] the markers in front of it (what the record pass takes as their number)
 };
 CF_DEV void text_cut_body(const DTextCut &c) {
@@ -331,6 +332,7 @@ CF_DEV void text_cut_body(const DTextCut &c) {
     uint64_t cut = 0, k = 0;
     if (n > c.posCap) { cut = c.nBytes; k = n; }         // (more markers than are kept: the record pass refuses the block)
     else if (c.last) { cut = c.nBytes; k = n; }
+    else if (c.fastq == 2) { k = n; cut = k ? (uint64_t)c.pos[k - 1] + 1 : 0; }
     else if (c.fastq) { k = n & ~3ull; cut = k ? (uint64_t)c.pos[k - 1] + 1 : 0; }
     else {
         k = n;

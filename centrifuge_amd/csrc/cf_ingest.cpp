@@ -543,10 +543,93 @@ void parseFastqChunk(const char *p, const char *e, bool firstOfFile, int trim5, 
     }
 }
 
+// TabbedPatternSource::readPair / ::read (pat.cpp:1159-1342) record by record, with parseName, parseSeq and parseQuals
+// (pat.cpp:1350-1503) as they are: a name runs to the first tab and a line end inside it ends the input; a sequence is every LETTER
+// up to the next tab, whatever lies between them (line ends included); the qualities are read until there are as many as the
+// sequence kept plus the 5' trim — fewer is tooFewQualities, more are skipped unseen — and then on to the field's end.
+void parseTabChunk(const char *p, const char *e, bool secondName, bool pairs, int trim5, int trim3, uint32_t globalSeed, ReadSoA &out, bool lastOfFile) {
+    out.hasQual = true;
+    if (out.qual.size() < out.seq.size()) out.qual.resize(out.seq.size(), (uint8_t)'I');
+    std::vector<uint8_t> s[2], q[2];
+    const char *name[2] = {nullptr, nullptr};
+    size_t nameLen[2] = {0, 0};
+    auto isnl = [](char c) { return c == '\n' || c == '\r'; };
+    // -1 in the reference: the input of this file ends here, the record is dropped
+    auto ranOff = [&]() {
+        if (!lastOfFile) throw std::runtime_error("Error: reads file does not look like a tabbed file: a record does not end with its line");
+        out.inputEnded = true;
+    };
+    auto parseName = [&](int m) -> bool {                                // pat.cpp:1350-1381 (the default name: the caller's, by the record's number)
+        name[m] = p;
+        while (p < e && *p != '\t') { if (isnl(*p)) { out.inputEnded = true; return false; } p++; }
+        if (p >= e) { out.inputEnded = true; return false; }
+        nameLen[m] = (size_t)(p - name[m]);
+        p++;
+        return true;
+    };
+    auto parseSeq = [&](int m) -> bool {                                 // pat.cpp:1389-1436
+        s[m].clear();
+        int begin = 0;
+        while (p < e && *p != '\t') {
+            const unsigned char ch = (unsigned char)*p++;
+            if (kT.alpha[ch] && begin++ >= trim5) s[m].push_back(kT.code[ch]);
+        }
+        if (p >= e) { ranOff(); return false; }
+        p++;
+        if (trim3 > 0) { if (s[m].size() > (size_t)trim3) s[m].resize(s[m].size() - (size_t)trim3); else s[m].clear(); }
+        return true;
+    };
+    // ct: the last character read (-1: the end of the input, behind a complete quality string)
+    auto parseQuals = [&](int m, int nm, int upto, int upto2, int &ct) -> bool {  // pat.cpp:1444-1503
+        q[m].clear();
+        const size_t need = s[m].size() + (size_t)std::max(0, trim5);
+        size_t qualsRead = 0;
+        int c = 0;
+        while (qualsRead < need) {
+            if (p >= e) { ranOff(); return false; }
+            c = (unsigned char)*p++;
+            if (c == ' ') throw std::runtime_error("Error: Encountered one or more spaces while parsing the quality string for read " + std::string(name[nm], nameLen[nm]) +
+                                                   ".  If this is a FASTQ file with integer (non-ASCII-encoded) qualities, try re-running with the --integer-quals option.");
+            if (std::isspace(c) || c == upto || c == upto2) break;
+            if (qualsRead >= (size_t)std::max(0, trim5)) {
+                if (c < 33) throw std::runtime_error("Saw ASCII character " + std::to_string(c) + " but expected 33-based Phred qual.");
+                q[m].push_back((uint8_t)c);
+            }
+            qualsRead++;
+        }
+        if (qualsRead < need) throw std::runtime_error("Error: Read " + std::string(name[nm], nameLen[nm]) + " has more read characters than quality values.");
+        q[m].resize(s[m].size());
+        while (c != upto && c != upto2) { if (p >= e) { c = -1; break; } c = (unsigned char)*p++; }
+        ct = c;
+        return true;
+    };
+    auto push = [&](int m, int nm, uint8_t kind) {
+        const uint32_t seed = cf_gen_rand_seed(s[m].data(), q[m].data(), s[m].size(), name[nm], nameLen[nm], globalSeed);
+        out.push(s[m].data(), q[m].data(), s[m].size(), name[nm], nameLen[nm], seed);
+        out.mate.push_back(kind);
+    };
+    while (p < e && !out.inputEnded) {
+        if (pairs && isnl(*p)) { while (p < e && isnl(*p)) p++; if (p >= e) break; }      // readPair skips vertical white space in front of a record
+        int ct = 0;
+        if (!parseName(0) || !parseSeq(0)) break;
+        if (!pairs) {                                                    // ::read: three fields, the rest of the line unseen
+            if (!parseQuals(0, 0, '\n', -2, ct)) break;
+            push(0, 0, 0);
+            continue;
+        }
+        if (!parseQuals(0, 0, '\t', '\n', ct)) break;
+        if (ct != '\t') { push(0, 0, 0); continue; }                     // three fields: an unpaired read
+        if (secondName) { if (!parseName(1)) break; }
+        if (!parseSeq(1) || !parseQuals(1, secondName ? 1 : 0, '\n', -2, ct)) break;
+        push(0, 0, 1);
+        push(1, secondName ? 1 : 0, 2);                                  // --tab5: the second mate takes the first mate's name
+    }
+}
+
 // ----------------------------------------------------------------------------------------
-ChunkedReader::ChunkedReader(std::vector<std::string> files, ReadFormat fmt, int trim5, int trim3, uint32_t globalSeed, int threads, bool pack, uint64_t startOffset, std::string startHead)
+ChunkedReader::ChunkedReader(std::vector<std::string> files, ReadFormat fmt, int trim5, int trim3, uint32_t globalSeed, int threads, bool pack, uint64_t startOffset, std::string startHead, bool tabPairs)
     : files_(std::move(files)), fmt_(fmt), trim5_(trim5), trim3_(trim3), globalSeed_(globalSeed),
-      parallel_(fmt == ReadFormat::Fasta || fmt == ReadFormat::Fastq), pack_(pack), startOffset_(startOffset), startHead_(std::move(startHead)) {
+      parallel_(fmt == ReadFormat::Fasta || fmt == ReadFormat::Fastq || fmt == ReadFormat::Tab5 || fmt == ReadFormat::Tab6), pack_(pack), tabPairs_(tabPairs), startOffset_(startOffset), startHead_(std::move(startHead)) {
     if (!parallel_) { seqSrc_.reset(new ReadSource(files_, fmt_, trim5_, trim3_)); return; }
     const int n = std::max(1, threads);
     maxInFlight_ = (size_t)n * 2 + 2;
@@ -568,7 +651,12 @@ ChunkedReader::~ChunkedReader() {
 // lines to match — the fallback for a stretch that has grown past a few blocks without an accepted candidate (a file whose
 // quality strings do not match its sequences record after record: the parser deals with those, as the reference's does; the
 // reader must not swallow the whole file into one block looking for a cut point).
-static size_t lastRecordStart(const char *bp, size_t len, bool fasta, bool lenient = false) {
+// lines (the tabbed formats): a record ends at every '\n' — the byte behind the last one that has a byte behind it.
+static size_t lastRecordStart(const char *bp, size_t len, bool fasta, bool lenient = false, bool lines = false) {
+    if (lines) {
+        for (size_t i = len; i-- > 1;) if (bp[i - 1] == '\n') return i;
+        return 0;
+    }
     if (fasta) {
         for (size_t i = len; i-- > 1;) if (bp[i] == '>') return i;
         return 0;
@@ -672,7 +760,7 @@ uint64_t behindNthByte(const char *p, size_t n, char c, uint64_t k) {
 // Where the block of a plain file that starts at pos (a record start) ends: the last record start in (pos, pos + kBlock] — a look
 // at the last 256 KiB of the block, further back if need be — or, for a record larger than the block, in the blocks behind it;
 // the end of the file when that comes first.
-uint64_t nextRecordCut(int fd, uint64_t pos, uint64_t fsize, size_t kBlock, bool fasta, const std::string &path) {
+uint64_t nextRecordCut(int fd, uint64_t pos, uint64_t fsize, size_t kBlock, bool fasta, const std::string &path, bool lines) {
     uint64_t end = pos + kBlock, cut = 0;
     std::vector<char> win;
     for (;;) {
@@ -681,11 +769,11 @@ uint64_t nextRecordCut(int fd, uint64_t pos, uint64_t fsize, size_t kBlock, bool
             const uint64_t ws = end - pos > T ? end - T : pos;
             win.resize((size_t)(end - ws));
             preadFull(fd, win.data(), win.size(), ws, path);
-            const size_t local = lastRecordStart(win.data(), win.size(), fasta);
+            const size_t local = lastRecordStart(win.data(), win.size(), fasta, false, lines);
             if (local) cut = ws + local;
             if (ws == pos) {
                 // nothing in the whole stretch passes the check: past a few blocks, the lenient rule (see lastRecordStart)
-                if (!cut && !fasta && end - pos > 4 * (uint64_t)kBlock) { const size_t l2 = lastRecordStart(win.data(), win.size(), false, true); if (l2) cut = ws + l2; }
+                if (!cut && !fasta && !lines && end - pos > 4 * (uint64_t)kBlock) { const size_t l2 = lastRecordStart(win.data(), win.size(), false, true); if (l2) cut = ws + l2; }
                 break;
             }
         }
@@ -697,6 +785,7 @@ uint64_t nextRecordCut(int fd, uint64_t pos, uint64_t fsize, size_t kBlock, bool
 void ChunkedReader::ioLoop() {
     // bytes per block: 32 MiB = ~280 k reads of 100 bases (CF_INGEST_BLOCK: the tests cut the input into many small blocks)
     const size_t kBlock = cfamd::cf_knob("CF_INGEST_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_INGEST_BLOCK"), nullptr, 10)) : (size_t)(32u << 20);
+    const bool lines = fmt_ == ReadFormat::Tab5 || fmt_ == ReadFormat::Tab6;
     try {
         for (const std::string &path : files_) {
             ByteSource src(path, (int)std::max<size_t>(1, parsers_.size()), startOffset_);      // plain / stdin / gzip (in-process) / bzip2; throws when it cannot be opened
@@ -710,7 +799,7 @@ void ChunkedReader::ioLoop() {
                 startOffset_ = 0;                            // (the first file only)
                 bool first = pos == 0;
                 while (pos < fsize) {
-                    const uint64_t cut = nextRecordCut(fd, pos, fsize, kBlock, fmt_ == ReadFormat::Fasta, path);
+                    const uint64_t cut = nextRecordCut(fd, pos, fsize, kBlock, fmt_ == ReadFormat::Fasta, path, lines);
                     Raw r;
                     r.first = first; first = false;
                     r.last = cut == fsize;
@@ -751,8 +840,8 @@ void ChunkedReader::ioLoop() {
                 const char *bp = buf.p.get();
                 size_t cut = buf.len;
                 if (!eof) {                                  // last record start inside the buffer
-                    cut = lastRecordStart(bp, buf.len, fmt_ == ReadFormat::Fasta);
-                    if (cut == 0 && fmt_ != ReadFormat::Fasta && buf.len > 4 * kBlock) cut = lastRecordStart(bp, buf.len, false, true);
+                    cut = lastRecordStart(bp, buf.len, fmt_ == ReadFormat::Fasta, false, lines);
+                    if (cut == 0 && fmt_ == ReadFormat::Fastq && buf.len > 4 * kBlock) cut = lastRecordStart(bp, buf.len, false, true);
                     if (cut == 0) continue;                  // one record larger than the block: keep reading
                 }
                 carry.assign(bp + cut, bp + buf.len);
@@ -805,7 +894,8 @@ void ChunkedReader::parseLoop() {
             }
             const char *p = r.data.p.get(), *e = p + r.data.len;
             if (fmt_ == ReadFormat::Fasta) parseFastaChunk(p, e, r.first, trim5_, trim3_, globalSeed_, out, r.last);
-            else parseFastqChunk(p, e, r.first, trim5_, trim3_, globalSeed_, out, r.last);
+            else if (fmt_ == ReadFormat::Fastq) parseFastqChunk(p, e, r.first, trim5_, trim3_, globalSeed_, out, r.last);
+            else parseTabChunk(p, e, fmt_ == ReadFormat::Tab6, tabPairs_, trim5_, trim3_, globalSeed_, out, r.last);
             if (pack_) out.pack();
         } catch (const std::exception &ex) {
             std::lock_guard<std::mutex> lk(mu_);
@@ -837,6 +927,7 @@ bool ChunkedReader::next(ReadSoA &out) {
         parseSequential(out, 1u << 16);
         return out.size() > 0;
     }
+    if (ended_) return false;
     std::unique_lock<std::mutex> lk(mu_);
     cv_.wait(lk, [&] { return !error_.empty() || done_.count(nextOut_) || (ioDone_ && nextOut_ == produced_); });
     if (!error_.empty()) throw std::runtime_error(error_);
@@ -846,6 +937,7 @@ bool ChunkedReader::next(ReadSoA &out) {
     out = std::move(it->second);
     done_.erase(it);
     nextOut_++;
+    ended_ = out.inputEnded;
     lk.unlock();
     cv_.notify_all();
     return true;

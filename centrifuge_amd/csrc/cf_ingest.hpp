@@ -69,10 +69,14 @@ struct ReadSoA {
     std::vector<uint32_t> seeds;
     std::vector<uint32_t> unnamedKeep;      // reads without a name that must stay unnamed (FASTQ records without a base letter)
     bool hasQual = false;
+    // tabbed input (parseTabChunk): per read 0 = an unpaired read, 1 / 2 = the first / second mate of a pair line (mates adjacent);
+    // inputEnded: the chunk holds a name with a line end inside it, where the reference stops reading the file ("done")
+    std::vector<uint8_t> mate;
+    bool inputEnded = false;
 
     size_t size() const { return off.size() - 1; }
     void clear() {
-        seq.clear(); off.assign(1, 0); names.clear(); nameOff.assign(1, 0); qual.clear(); seeds.clear(); unnamedKeep.clear();
+        seq.clear(); off.assign(1, 0); names.clear(); nameOff.assign(1, 0); qual.clear(); seeds.clear(); unnamedKeep.clear(); mate.clear(); inputEnded = false;
         pk.valid = false; pk.appendable = true; pk.nReads = pk.nWords = pk.nBases = pk.nN = 0; pk.maxLen = 0;
     }
     void push(const uint8_t *s, const uint8_t *q, size_t len, const char *name, size_t nameLen, uint32_t seed);
@@ -94,8 +98,10 @@ public:
     // startOffset: where in the (first, plain) file to begin — a record start (a run that changes over from the device text path).
     // For a BGZF file it is the byte a member starts at, and startHead the text in front of that member's: from a record start to
     // the member's first byte (what cf_batch_upload_bgzf handed back as the tail of the members before it).
+    // tabPairs: a tabbed line with more than three fields is a pair (TabbedPatternSource::readPair: files named by --tab5 / --12 /
+    // --tab6); false: every line gives one read, what follows its third field is skipped (TabbedPatternSource::read: -U / -1 / -2 files)
     ChunkedReader(std::vector<std::string> files, ReadFormat fmt, int trim5, int trim3, uint32_t globalSeed, int threads, bool pack = false, uint64_t startOffset = 0,
-                  std::string startHead = std::string());
+                  std::string startHead = std::string(), bool tabPairs = true);
     ~ChunkedReader();
     // Next chunk of parsed reads in input order; false at the end.  Reads whose name was empty
     // come back with an empty name (the caller substitutes the read's ordinal, pat.cpp:838-842).
@@ -126,6 +132,8 @@ private:
     uint32_t globalSeed_;
     bool parallel_;
     bool pack_ = false;
+    bool tabPairs_ = true;
+    bool ended_ = false;                     // a chunk with inputEnded was handed out: nothing behind it is
     uint64_t startOffset_ = 0;
     std::string startHead_;
     std::unique_ptr<ReadSource> seqSrc_;     // raw / command-line formats: sequential path
@@ -153,7 +161,8 @@ private:
 
 // a plain file dealt out as ranges (the reader's own blocks, and the front end's device text path): where the block that starts at
 // pos — a record start — ends (a record start, or the end of the file), and the bytes of a range
-uint64_t nextRecordCut(int fd, uint64_t pos, uint64_t fsize, size_t kBlock, bool fasta, const std::string &path);
+// lines: a record ends at every '\n' (the tabbed formats); `fasta` is not looked at then
+uint64_t nextRecordCut(int fd, uint64_t pos, uint64_t fsize, size_t kBlock, bool fasta, const std::string &path, bool lines = false);
 void readFileRange(int fd, char *dst, size_t n, uint64_t off, const std::string &path);
 // (mates on the text path: the second file is cut where it holds as many records as the first file's block)
 uint64_t countByte(const char *p, size_t n, char c);
@@ -164,5 +173,10 @@ uint64_t behindNthByte(const char *p, size_t n, char c, uint64_t k);       // ~0
 // followed by nothing but line ends) is not a read (FastaPatternSource::read bails out, pat.cpp:764-783)
 void parseFastaChunk(const char *p, const char *e, bool firstOfFile, int trim5, int trim3, uint32_t globalSeed, ReadSoA &out, bool lastOfFile = false);
 void parseFastqChunk(const char *p, const char *e, bool firstOfFile, int trim5, int trim3, uint32_t globalSeed, ReadSoA &out, bool lastOfFile = true);
+// whole lines of a tabbed file (TabbedPatternSource, pat.cpp:1159-1503): name \t seq \t qual [\t [name2 \t] seq2 \t qual2]; secondName:
+// --tab6.  out.mate says which reads are mates of a pair line (`pairs`, see ChunkedReader).  A record that runs over the end of the
+// chunk is the end of the input in the file's last chunk (the reference's EOF) and an error anywhere else: chunks are cut behind a
+// '\n', so a record whose sequence field runs over a line end — legal under readPair — parses only where it lies inside one chunk.
+void parseTabChunk(const char *p, const char *e, bool secondName, bool pairs, int trim5, int trim3, uint32_t globalSeed, ReadSoA &out, bool lastOfFile = true);
 
 }  // namespace cfamd

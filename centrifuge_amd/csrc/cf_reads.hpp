@@ -1,7 +1,7 @@
 // cf_reads.hpp — the sequential read sources of the command-line front end: raw (one sequence per line) and
 // command-line sequences into base codes 0..4, names and qualities.  Behaviour follows the reference's parsers
 // (RawPatternSource pat.h:1478-1585, VectorPatternSource pat.cpp:456-546; alphabet.cpp:298-319); the code is our
-// own.  FASTA / FASTQ files go through the chunk parsers of cf_ingest.cpp.
+// own.  FASTA / FASTQ files and tabbed files (--tab5 / --12 / --tab6) go through the chunk parsers of cf_ingest.cpp.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -13,7 +13,7 @@ namespace cfamd {
 
 class ByteSource;
 
-enum class ReadFormat { Fasta, Fastq, Raw, CmdLine };
+enum class ReadFormat { Fasta, Fastq, Raw, CmdLine, Tab5, Tab6 };
 
 struct ReadRec {
     std::string name;

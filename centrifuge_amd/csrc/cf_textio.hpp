@@ -10,6 +10,15 @@
 //          lines whose characters are A C G T N in either case, at least one of them
 //   FASTQ  four lines per record: '@' + non-empty name without '\r'; a non-empty line of A C G T N in either case; a line that
 //          starts with '+'; as many quality characters (all >= 33) as bases; the block ends with the last record's '\n'
+//   TAB5 / TAB6 (--tab5 / --12 / --tab6; the host side: parseTabChunk after TabbedPatternSource::readPair, pat.cpp:1217-1503)
+//          the block ends with '\n'; no '\r' anywhere and no empty line; EVERY line has the same number of tab-separated fields — 3
+//          (an unpaired read: name seq qual) or the pair count (5: name seq1 qual1 seq2 qual2; TAB6, 6: name1 seq1 qual1 name2 seq2
+//          qual2) — a block with both kinds is refused with kTxFieldCount, a line with any other count with kTxLineCount; names are
+//          non-empty; a sequence field is non-empty and holds A C G T N in either case only (a tab is neither a base nor a
+//          quality: the fields are delimited first, by every tab of the line); each quality field is exactly as long as its
+//          sequence, every character of it >= 33.  A 3-field record r is read r - skip of the batch, a pair record reads
+//          2 (r - skip) and 2 (r - skip) + 1; under TAB5 the second mate's readID is the first's; a mate's seed starts from seed0
+//          with its own name, bases and qualities; trim5 / trim3 window each mate's fields as they window a FASTQ record's lines.
 // Egress: the default eight columns of AlnSinkSam::appendMate — or any other list of its columns (fmt_cols_*_body, at the end) — (aln_sink.h:2279-2337; centrifuge.cpp:520) are formatted here from
 // the narrow rows the batch leaves on the device, the readID copied out of the uploaded block (aln_sink.h:2203-2217), into a
 // buffer the host only write()s; and the part of SpeciesMetrics (aln_sink.h:142-172) the per-taxon counters of count_body do not
@@ -23,14 +32,23 @@ namespace cfamd {
 
 constexpr uint32_t kTextPiece = 64;                     // bytes per thread of the two marker passes
 constexpr uint32_t kTextPad = 128;                      // zero bytes the uploaded block is followed by (whole-piece and whole-word loads)
-enum : uint32_t { kTextFasta = 0, kTextFastq = 1 };
+enum : uint32_t { kTextFasta = 0, kTextFastq = 1, kTextTab5 = 2, kTextTab6 = 3 };
 // why a block is not in the plain form (TextStatus::flags; any bit = the host parses it)
 enum : uint32_t {
     kTxBadStart = 1u, kTxNoNameEnd = 2u, kTxEmptyName = 4u, kTxCarriageReturn = 8u, kTxBadBase = 16u, kTxEmptySeq = 32u,
     kTxBadPlus = 64u, kTxQualLen = 128u, kTxBadQual = 256u, kTxLineCount = 512u, kTxTooMany = 1024u,
     kTxMateCount = 2048u,                                // (made by the host: the two blocks of a paired upload hold different numbers of records)
-    kTxTailRoom = 4096u                                  // (made by the host: a BGZF upload leaves more text behind its last whole record than the slot keeps room for)
+    kTxTailRoom = 4096u,                                 // (made by the host: a BGZF upload leaves more text behind its last whole record than the slot keeps room for)
+    kTxFieldCount = 8192u,                               // a tabbed block holds pair lines AND three-field lines (made by text_tab_kind from the two bits below)
+    kTxTabSingle = 1u << 30, kTxTabPair = 1u << 31       // the record pass: a line of three fields / of the pair count was seen.  Never reported: text_tab_kind takes them out
 };
+// what a tabbed block's record pass left in TextStatus::flags -> the flags to report; true: the block's lines are pairs
+inline bool text_tab_kind(uint32_t &flags) {                        // (host code: after the status came back)
+    const bool pairs = (flags & kTxTabPair) != 0;
+    if (pairs && (flags & kTxTabSingle)) flags |= kTxFieldCount;
+    flags &= ~(kTxTabSingle | kTxTabPair);
+    return pairs;
+}
 
 constexpr uint32_t kTextStripes = 64;                   // the block's sums are kept in that many places (a wavefront adds to one of them:
                                                         // ten thousand atomics on ONE address took most of the record pass), added up by the host
@@ -237,13 +255,14 @@ CF_DEV uint32_t tx_quals(const uint8_t *text, uint64_t pos, uint64_t e, uint32_t
     return flags;
 }
 // the name line from `from` to its '\n' (which must lie before `lim`): the name's term of the seed, the readID's length
-CF_DEV uint32_t tx_name(TxCursor &c, uint64_t lim, uint32_t &r, uint32_t &nameLen, uint32_t &idLen) {
+// (stop: what ends the name — the tab behind a tabbed record's name field)
+CF_DEV uint32_t tx_name(TxCursor &c, uint64_t lim, uint32_t &r, uint32_t &nameLen, uint32_t &idLen, uint32_t stop = '\n') {
     uint32_t flags = 0, j = 0, ws = 0xffffffffu, p1 = 0, p2 = 0;
     bool slash = false;
     for (;;) {
         if (c.at >= lim) { flags |= kTxNoNameEnd; break; }
         const uint32_t ch = c.next();
-        if (ch == '\n') break;
+        if (ch == stop) break;
         if (ch == '\r') flags |= kTxCarriageReturn;
         if (ch == '/') slash = true;
         if (!slash) r ^= (uint32_t)(int32_t)(int8_t)ch << ((j & 3u) << 3);
@@ -262,12 +281,95 @@ struct TextCounts { uint64_t nMarkers; uint32_t nRec; bool fits; };
 CF_DEV TextCounts text_counts(const DTextRec &d) {
     TextCounts c;
     c.nMarkers = *d.total;
-    const uint64_t rec = d.format == kTextFasta ? c.nMarkers : c.nMarkers >> 2;
+    const uint64_t rec = d.format == kTextFastq ? c.nMarkers >> 2 : c.nMarkers;          // (a tabbed record is a line)
     c.fits = c.nMarkers <= d.posCap && rec <= d.recCap;
     c.nRec = c.fits ? (uint32_t)rec : 0u;
     return c;
 }
-CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
+// one mate of a tabbed record: its bases [s0, s1) and qualities [q0, q1), fields the caller has delimited by the line's tabs (so
+// the 8-byte paths of tx_bases / tx_quals, which never read a field's last bytes as part of a whole word beyond its end, see no
+// tab).  trim5 / trim3 window both as they window a FASTQ record's lines.  -> flags; len, seed (^=), where the window starts
+CF_DEV uint32_t tx_tab_mate(const DTextRec &d, uint64_t s0, uint64_t s1, uint64_t q0, uint64_t q1, uint32_t &seed, uint32_t &len, uint32_t &seqOff, uint32_t &qualOff) {
+    uint32_t flags = 0;
+    const uint64_t all = s1 > s0 ? s1 - s0 : 0;
+    const uint64_t t5 = d.trim5 < all ? d.trim5 : all, keep = all - t5 > d.trim3 ? all - t5 - d.trim3 : 0;
+    const uint64_t b0 = s0 + t5, b1 = b0 + keep;
+    uint32_t unused = 0, cnt = 0;
+    len = 0;
+    seqOff = (uint32_t)b0; qualOff = (uint32_t)(q0 + t5);
+    if (all == 0) return kTxEmptySeq;
+    if (b0 > s0) flags |= tx_bases(d.text, s0, b0, unused, cnt);
+    flags |= tx_bases(d.text, b0, b1, seed, len);
+    if (s1 > b1) flags |= tx_bases(d.text, b1, s1, unused, cnt);
+    if (q1 < q0 || q1 - q0 != all) return flags | kTxQualLen;
+    const uint64_t w0 = q0 + t5, w1 = w0 + keep;
+    if (w0 > q0) flags |= tx_quals(d.text, q0, w0, unused);
+    flags |= tx_quals(d.text, w0, w1, seed);
+    if (q1 > w1) flags |= tx_quals(d.text, w1, q1, unused);
+    if (len == 0) flags |= kTxEmptySeq;
+    return flags;
+}
+// a tabbed record: line r of the block, one thread.  -> flags; len: the bases kept of both mates; words: their packed words
+CF_DEV uint32_t text_tab_record(const DTextRec &d, uint32_t r, bool kept, uint32_t &len, uint32_t &words, uint32_t &mx) {
+    uint32_t flags = 0;
+    const uint64_t ls = r ? (uint64_t)d.pos[r - 1] + 1 : 0, le = d.pos[r];
+    // the line's tabs (and any '\r'), eight bytes at a time; the places of the first five in scalars of their own
+    uint32_t nt = 0;
+    uint64_t t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+    for (uint64_t p = ls; p < le; p += 8) {
+        const uint64_t x = tx_load8(d.text, p);
+        const uint64_t in = le - p >= 8 ? ~0ull : (1ull << (8 * (le - p))) - 1;
+        uint64_t m = tx_match8(x, '\t') & in;
+        if (tx_match8(x, '\r') & in) flags |= kTxCarriageReturn;
+        while (m) {
+            const uint64_t at = p + (uint64_t)(cf_ctz64(m) >> 3);
+            if (nt == 0) t0 = at; else if (nt == 1) t1 = at; else if (nt == 2) t2 = at; else if (nt == 3) t3 = at; else if (nt == 4) t4 = at;
+            nt++; m &= m - 1;
+        }
+    }
+    const uint32_t pairTabs = d.format == kTextTab6 ? 5u : 4u;
+    const bool pair = nt == pairTabs;
+    if (nt != 2 && !pair) return flags | kTxLineCount;
+    flags |= pair ? kTxTabPair : kTxTabSingle;
+    // names: a term of the seed each (from 0: XORed into the mate's seed below), the readID's length
+    TxCursor c;
+    uint32_t term1 = 0, term2, nameLen = 0, idLen1 = 0, idLen2, idOff1 = (uint32_t)ls, idOff2;
+    c.seek(d.text, ls);
+    flags |= tx_name(c, t0 + 1, term1, nameLen, idLen1, '\t');
+    term2 = term1; idLen2 = idLen1; idOff2 = idOff1;
+    uint64_t s2 = t2 + 1, e2 = t3, q2 = t3 + 1;                            // TAB5: seq2 and qual2 behind the third tab
+    if (pair && d.format == kTextTab6) {
+        term2 = 0;
+        c.seek(d.text, t2 + 1);
+        flags |= tx_name(c, t3 + 1, term2, nameLen, idLen2, '\t');
+        idOff2 = (uint32_t)(t2 + 1);
+        s2 = t3 + 1; e2 = t4; q2 = t4 + 1;
+    }
+    uint32_t seed1 = d.seed0 ^ term1, len1 = 0, so1, qo1;
+    flags |= tx_tab_mate(d, t0 + 1, t1, t1 + 1, pair ? t2 : le, seed1, len1, so1, qo1);
+    const uint64_t w = pair ? 2 * (uint64_t)(r - d.skip) : (uint64_t)(r - d.skip);
+    if (kept) {
+        d.idOff[w] = d.textBase + idOff1; d.idLen[w] = idLen1; d.seqOff[w] = d.textBase + so1;
+        if (d.qualOff) d.qualOff[w] = d.textBase + qo1;
+        d.rlen[w] = len1; d.seeds[w] = seed1;
+    }
+    len = len1; words = (len1 + 31u) >> 5; mx = len1;
+    if (pair) {
+        uint32_t seed2 = d.seed0 ^ term2, len2 = 0, so2, qo2;
+        flags |= tx_tab_mate(d, s2, e2, q2, le, seed2, len2, so2, qo2);
+        if (kept) {
+            d.idOff[w + 1] = d.textBase + idOff2; d.idLen[w + 1] = idLen2; d.seqOff[w + 1] = d.textBase + so2;
+            if (d.qualOff) d.qualOff[w + 1] = d.textBase + qo2;
+            d.rlen[w + 1] = len2; d.seeds[w + 1] = seed2;
+        }
+        len += len2; words += (len2 + 31u) >> 5; mx = len2 > mx ? len2 : mx;
+    }
+    return flags;
+}
+// FMT: the body for FASTA / FASTQ (false: d.format says which, the pass as it was) or for the tabbed formats (true) — two
+// instantiations, so that the first keeps its registers
+template <bool TAB>
+CF_DEV void text_record_body_t(const DTextRec &d, uint32_t r) {
     uint32_t flags = 0, len = 0;
     const TextCounts tc = text_counts(d);
     const bool live = r < tc.nRec;
@@ -275,8 +377,9 @@ CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
         // the checks on the block as a whole
         if (!tc.fits) flags |= kTxTooMany;
         else if (d.nBytes) {
-            if (d.text[0] != (d.format == kTextFasta ? '>' : '@')) flags |= kTxBadStart;
-            if (d.format == kTextFastq && ((tc.nMarkers & 3u) || d.text[d.nBytes - 1] != '\n')) flags |= kTxLineCount;
+            if (!TAB && d.text[0] != (d.format == kTextFasta ? '>' : '@')) flags |= kTxBadStart;
+            if (!TAB && d.format == kTextFastq && ((tc.nMarkers & 3u) || d.text[d.nBytes - 1] != '\n')) flags |= kTxLineCount;
+            if (TAB && d.text[d.nBytes - 1] != '\n') flags |= kTxLineCount;
             if (tc.nRec == 0) flags |= kTxBadStart;
         }
     }
@@ -284,7 +387,9 @@ CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
     const bool kept = live && r >= d.skip;
     const uint64_t w = (uint64_t)d.stride * (r - d.skip) + d.mate;      // the read's number in the batch
     const bool trim = (d.trim5 | d.trim3) != 0;                         // (the same for every thread of the launch)
-    if (live) {
+    uint32_t tabWords = 0, tabMax = 0;
+    if (TAB) { if (live) flags |= text_tab_record(d, r, kept, len, tabWords, tabMax); }
+    else if (live) {
         uint32_t seed = d.seed0, nameLen = 0, idLen = 0, idOff, seqOff, qualOff = 0;
         TxCursor c;
         if (d.format == kTextFasta) {
@@ -350,8 +455,8 @@ CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
         }
     }
     // the block's sums: over the wavefront first, one set of atomics per wavefront
-    unsigned long long words = kept ? (len + 31u) >> 5 : 0u, bases = kept ? len : 0u;
-    uint32_t mx = kept ? len : 0u;
+    unsigned long long words = kept ? (TAB ? tabWords : (len + 31u) >> 5) : 0u, bases = kept ? len : 0u;
+    uint32_t mx = kept ? (TAB ? tabMax : len) : 0u;
     for (int m = CF_WAVE / 2; m > 0; m >>= 1) {
         words += cf_shfl_xor(words, m); bases += cf_shfl_xor(bases, m);
         const uint32_t o = cf_shfl_xor(mx, m); mx = o > mx ? o : mx;
@@ -364,6 +469,10 @@ CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
         if (mx > d.st->maxLen) cf_atomic_max(&d.st->maxLen, mx);      // (the plain read only spares atomics that would change nothing)
         if (flags) cf_atomic_or(&d.st->flags, flags);
     }
+}
+
+CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {
+    if (d.format >= kTextTab5) text_record_body_t<true>(d, r); else text_record_body_t<false>(d, r);
 }
 
 // ---- pass 4 (behind the exclusive sums of the reads' word counts): the 2-bit words and the N masks, one thread per record.

@@ -298,10 +298,20 @@ cf_status cf_results_narrow_expand(const cf_index *, const cf_results_narrow *, 
  * parse (one status word crosses the link): the number of reads sizes the slot. */
 #define CF_TEXT_FASTA 0
 #define CF_TEXT_FASTQ 1
+/* Tabbed blocks (--tab5 / --12 / --tab6; TabbedPatternSource, pat.cpp:1159-1503): whole lines,  name \t seq \t qual  (an unpaired read)
+ * or  name \t seq1 \t qual1 \t seq2 \t qual2  (TAB5) /  name1 \t seq1 \t qual1 \t name2 \t seq2 \t qual2  (TAB6).  The plain form: the block
+ * ends with '\n', no '\r', no empty line; every line has the SAME number of fields, 3 or the pair count (both kinds in one block:
+ * CF_TEXT_FIELD_COUNT; any other count: the line-count bit); non-empty names; non-empty sequences of A C G T N in either case;
+ * quality fields as long as their sequences, every character >= 33.  text2 must be NULL (CF_ERR_ARG) and cf_batch_upload_bgzf_pair
+ * refuses these formats (CF_ERR_ARG): both mates lie in one line.  info->paired says what the block held: with pairs n_reads is twice
+ * the records and reads 2q, 2q+1 are the mates of query q, as with text2; max_reads and the skip count records. */
+#define CF_TEXT_TAB5 2
+#define CF_TEXT_TAB6 3
+#define CF_TEXT_FIELD_COUNT 8192u
 typedef struct {
     const char *text;          /* n_bytes of the file, from a record start to a record end; pinned memory makes the copy a DMA */
     uint64_t n_bytes;          /* < 2^32 - 65536                                                       */
-    int32_t  format;           /* CF_TEXT_FASTA | CF_TEXT_FASTQ                                        */
+    int32_t  format;           /* CF_TEXT_FASTA | CF_TEXT_FASTQ | CF_TEXT_TAB5 | CF_TEXT_TAB6          */
     uint32_t global_seed;      /* --seed (cf_gen_rand_seed's last argument)                            */
     uint64_t max_reads;        /* 0 = every record; else only the block's first max_reads records (pairs, with text2) (-u) */
     const char *text2;         /* mates: the block of the second file that holds the SAME NUMBER of records (any other number */
@@ -311,6 +321,8 @@ typedef struct {
     uint64_t n_reads, n_bases;
     uint32_t max_len;
     uint32_t irregular;        /* 0 = the slot holds the block's reads; else why the block is not in the plain form (a bit set) */
+    uint32_t paired;           /* 1 = reads 2q and 2q+1 are the mates of query q (text2, the _pair call, a tabbed block of pair lines) */
+    uint32_t reserved;
 } cf_text_info;
 cf_status cf_batch_upload_text(cf_batch *, const cf_text_reads *, void *hip_stream, cf_text_info *info);
 /* BGZF members in (bgzip, htslib: a gzip file of independent members of at most 64 KiB that carry their own compressed size in a
