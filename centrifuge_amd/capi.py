@@ -158,11 +158,28 @@ EXPORTS = [
     "cf_index_text_verify_rate", "cf_index_text_verify_build_ms", "cf_index_wide_ftab_chars", "cf_index_occ_planes", "cf_index_occ_planes_build_ms", "cf_index_resolve_rate", "cf_index_resolve_build_ms", "cf_index_walk_bound", "cf_index_resolve_by_position", "cf_slot_estimate_bytes", "cf_batch_reclassify_async", "cf_comm_init_all", "cf_comm_destroy", "cf_counts_allreduce_group", "cf_stream_create", "cf_stream_destroy", "cf_device_count", "cf_device_numa_node", "cf_thread_bind_near_device",
     "cf_report_adopt_counts", "cf_debug_scan", "cf_host_alloc", "cf_host_free", "cf_batch_alloc", "cf_batch_upload_packed_async", "cf_classify_async", "cf_batch_download_async",
     "cf_batch_submit", "cf_batch_wait", "cf_batch_upload", "cf_batch_set_limits", "cf_batch_upload_bgzf", "cf_batch_upload_bgzf_pair",
+    "cf_batch_wait_text_bgzf", "cf_batch_deflate_ms", "cf_bgzf_eof", "cf_bgzf_deflate_host",
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
 ]
 
 _lib = None
+
+
+def bgzf_eof():
+    """the empty member that ends a BGZF file"""
+    out = (C.c_uint8 * 28)()
+    lib().cf_bgzf_eof(out)
+    return bytes(out)
+
+
+def bgzf_deflate_host(text):
+    """text (bytes) as BGZF members made on the host (zlib, level 1)"""
+    text = bytes(text)
+    cap = len(text) + 64 * (len(text) // 64 + 1)
+    out, n = (C.c_uint8 * cap)(), C.c_uint64(0)
+    _check(lib().cf_bgzf_deflate_host(text, len(text), out, cap, C.byref(n)))
+    return bytes(out[:n.value])
 
 
 def lib():
@@ -230,6 +247,9 @@ def lib():
         "cf_batch_upload_bgzf": (i32, [vp, C.POINTER(BgzfReads), vp, C.POINTER(TextInfo), C.POINTER(BgzfInfo)]),
         "cf_batch_upload_bgzf_pair": (i32, [vp, C.POINTER(BgzfReads), C.POINTER(BgzfReads), vp, C.POINTER(TextInfo), C.POINTER(BgzfInfo), C.POINTER(BgzfInfo)]),
         "cf_batch_wait_text": (i32, [vp, C.POINTER(ResultsText)]),
+        "cf_batch_wait_text_bgzf": (i32, [vp, C.POINTER(ResultsText), C.POINTER(u64)]),
+        "cf_batch_deflate_ms": (i32, [vp, C.POINTER(C.c_float)]),
+        "cf_bgzf_eof": (None, [vp]), "cf_bgzf_deflate_host": (i32, [cp, u64, vp, u64, C.POINTER(u64)]),
         "cf_text_column_of": (C.c_int32, [cp]), "cf_batch_set_text_columns": (i32, [vp, vp, u32]),
         "cf_batch_set_text_trim": (i32, [vp, u32, u32]), "cf_batch_set_text_skip": (i32, [vp, u64]),
         "cf_counts_get_single": (i32, [vp, vp]),
@@ -697,6 +717,22 @@ class Slot:
         tuples = np.frombuffer(C.string_at(r.tuples, 4 * r.n_tuple_words), dtype=np.uint32).copy() if r.n_tuple_words else np.zeros(0, np.uint32)
         return text, tuples, {"n_queries": r.n_queries, "total_rows": r.total_rows, "planned_sa_rows": r.planned_sa_rows, "row_passes": r.row_passes,
                               "slow_post": r.slow_post, "slow_score": r.slow_score}
+
+    def wait_text_bgzf(self):
+        """-> the batch's rows as whole BGZF members deflated on the device (bytes: they inflate to what wait_text() returns), that
+        text's size, the tuples and info of wait_text()"""
+        r, n = ResultsText(), C.c_uint64(0)
+        _check(self.L.cf_batch_wait_text_bgzf(self.h, C.byref(r), C.byref(n)))
+        members = C.string_at(r.text, r.n_bytes) if r.n_bytes else b""
+        tuples = np.frombuffer(C.string_at(r.tuples, 4 * r.n_tuple_words), dtype=np.uint32).copy() if r.n_tuple_words else np.zeros(0, np.uint32)
+        return members, n.value, tuples, {"n_queries": r.n_queries, "total_rows": r.total_rows, "planned_sa_rows": r.planned_sa_rows, "row_passes": r.row_passes,
+                                          "slow_post": r.slow_post, "slow_score": r.slow_score}
+
+    def deflate_ms(self):
+        """device ms of the deflate kernel of the last wait_text_bgzf()"""
+        ms = C.c_float()
+        _check(self.L.cf_batch_deflate_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def resubmit(self, streams):
         """plan + kernels + download once more over the reads the slot holds since its last submit (nothing is uploaded);

@@ -55,6 +55,7 @@ struct Opts {
     int slots = 2;                                      // --slots: GPU threads (batch slots, each with its stream) per device
     bool slotsSet = false;
     int devInflate = 1;                                 // --device-inflate off | unpaired | all: which BGZF inputs are inflated on the device (0, 1, 2)
+    bool outBgzf = false;                               // --out-bgzf: the classification output is one BGZF file (the device text path's blocks are deflated on the device)
     bool hostIo = false;                                // --host-io: the parser pool and the formatter threads for every input (no device text path)
     int smallRangeRows = 0;                             // --small-range-rows: cf_index_options::small_range_rows (0 = automatic, -1 = off)
     double hbmBudgetGb = 0;                             // --hbm-budget-gb: cf_index_options::hbm_budget_bytes (0 = what the device has free)
@@ -95,6 +96,9 @@ void usage(std::FILE *f) {
         " Classification:  -k <int> (5)  --min-hitlen <int> (22)  --host-taxids <t,..>  --exclude-taxids <t,..>\n"
         "          --classification-rank <strain|species|genus|family|order|class|phylum>  --no-traverse\n"
         " Output:  -S <file>  --report-file <file> (centrifuge_report.tsv)  --no-abundance  --tab-fmt-cols <c,..>  --out-fmt tab|sam  -t/--time\n"
+        "          --out-bgzf (the classification output — -S or stdout: header line, rows, --separator markers, the SAM form — as one BGZF\n"
+        "          file, the blocked gzip of bgzip / htslib, that inflates to the bytes the run prints without the flag; rows formatted on\n"
+        "          the device are deflated there and cross the link compressed, the rest is deflated by zlib; the report stays plain)\n"
         " Other:   -p/--threads <int> (host formatting threads)  --seed <int>  --batch <int>  --reorder --mm (accepted)\n"
         " GPUs:    --gpus <N|all> (index replicated on N devices from --device <int> on, batches dealt to them, per-taxon counters\n"
         "          all-reduced with RCCL, output in input order)  --gpu-list <d,..>  --slots <int> (batches in flight per device, 2)\n"
@@ -195,6 +199,7 @@ Opts parse(int argc, const char **argv) {
         else if (a == "--gpu-list") { for (auto &x : splitComma(val())) o.gpuList.push_back(std::atoi(x.c_str())); }
         else if (a == "--slots") { o.slots = std::atoi(val().c_str()); o.slotsSet = true; if (o.slots < 1) die("--slots arg must be at least 1"); }
         else if (a == "--host-io") o.hostIo = true;
+        else if (a == "--out-bgzf") o.outBgzf = true;
         else if (a == "--device-inflate") {
             const std::string m = val();
             if (m == "off") o.devInflate = 0; else if (m == "unpaired") o.devInflate = 1; else if (m == "all") o.devInflate = 2;
@@ -409,6 +414,9 @@ struct GpuThread {
     std::string zHead;                              // the text in front of the run in hand (the tail of the run before it)
     std::string zHead2;                             // ... of the second file of mates
     std::string tabText;                            // a tabbed block parsed on the host: the text of its runs of pairs / unpaired reads, one behind the other
+    std::vector<char> zText;                        // --out-bgzf: a block the host formatted, deflated (cf_bgzf_deflate_host)
+    uint64_t zOutText = 0, zOutBytes = 0, zOutBatches = 0;   // ... and the batches deflated on the device: their text, their members, k_deflate's ms
+    double zOutMs = 0;
 };
 
 struct Runner {
@@ -699,6 +707,22 @@ struct Runner {
         }
     }
 
+    // --out-bgzf: text the host holds as BGZF members (cf_bgzf_deflate_host) in `z`
+    static void bgzfHost(const char *text, uint64_t n, std::vector<char> &z) {
+        z.resize((size_t)(n + 64 * (n / 64 + 1)));
+        uint64_t got = 0;
+        CF_TRY(cf_bgzf_deflate_host(text, n, z.data(), z.size(), &got));
+        z.resize((size_t)got);
+    }
+    std::vector<char> zOut;
+    // host-formatted text into the classification output, in the order of the calls
+    void putOut(const char *text, size_t n) {
+        if (!n) return;
+        if (!o.outBgzf) { if (std::fwrite(text, 1, n, out) != n) die("error writing the classification output"); return; }
+        bgzfHost(text, n, zOut);                           // (one caller at a time: the writer, or the output thread behind waitWrite)
+        if (std::fwrite(zOut.data(), 1, zOut.size(), out) != zOut.size()) die("error writing the classification output");
+    }
+
     // n bytes at `at` of the output file through a mapping of that stretch; false = the file cannot be mapped (the caller writes)
     bool copyIntoFile(const char *text, uint64_t n, uint64_t at) {
         if (n == 0) return true;
@@ -815,7 +839,13 @@ struct Runner {
             CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
             lap(g.tm.create);
             cf_results_text res{};
-            CF_TRY(cf_batch_wait_text(g.slot, &res));
+            uint64_t plainBytes = 0;
+            if (o.outBgzf) {
+                CF_TRY(cf_batch_wait_text_bgzf(g.slot, &res, &plainBytes));
+                float ms = 0;
+                CF_TRY(cf_batch_deflate_ms(g.slot, &ms));
+                g.zOutText += plainBytes; g.zOutBytes += res.n_bytes; g.zOutMs += ms; g.zOutBatches++;
+            } else CF_TRY(cf_batch_wait_text(g.slot, &res));
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
             text = res.text; nText = res.n_bytes;
@@ -912,6 +942,7 @@ struct Runner {
                 }
                 text = g.tabText.data(); nText = g.tabText.size();
             }
+            if (o.outBgzf) { bgzfHost(text, nText, g.zText); text = g.zText.data(); nText = g.zText.size(); }
         }
         // the block's place in the output: behind the blocks before it
         const uint64_t at = outChain.enter(b.tIdx);
@@ -982,7 +1013,13 @@ struct Runner {
             CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
             lap(g.tm.create);
             cf_results_text res{};
-            CF_TRY(cf_batch_wait_text(g.slot, &res));
+            uint64_t plainBytes = 0;
+            if (o.outBgzf) {
+                CF_TRY(cf_batch_wait_text_bgzf(g.slot, &res, &plainBytes));
+                float ms = 0;
+                CF_TRY(cf_batch_deflate_ms(g.slot, &ms));
+                g.zOutText += plainBytes; g.zOutBytes += res.n_bytes; g.zOutMs += ms; g.zOutBatches++;
+            } else CF_TRY(cf_batch_wait_text(g.slot, &res));
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
             text = res.text; nText = res.n_bytes;
@@ -1065,7 +1102,13 @@ struct Runner {
             CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
             lap(g.tm.create);
             cf_results_text res{};
-            CF_TRY(cf_batch_wait_text(g.slot, &res));
+            uint64_t plainBytes = 0;
+            if (o.outBgzf) {
+                CF_TRY(cf_batch_wait_text_bgzf(g.slot, &res, &plainBytes));
+                float ms = 0;
+                CF_TRY(cf_batch_deflate_ms(g.slot, &ms));
+                g.zOutText += plainBytes; g.zOutBytes += res.n_bytes; g.zOutMs += ms; g.zOutBatches++;
+            } else CF_TRY(cf_batch_wait_text(g.slot, &res));
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
             text = res.text; nText = res.n_bytes;
@@ -1100,7 +1143,7 @@ struct Runner {
     template <typename Hms>
     void endInput(int idx, const Hms &hms) {
         waitWrite();
-        std::fputs("#File_End_Here\n", out);
+        putOut("#File_End_Here\n", 15);
         std::fflush(out);
         writeReport(rep, "centrifuge_report_" + std::to_string(idx) + ".tsv", hms);
         CF_TRY(cf_report_reset_counts(rep));              // counters only: the reference keeps its observed tuples (aln_sink.h:84-91)
@@ -1154,7 +1197,7 @@ struct Runner {
                 const auto w0 = std::chrono::steady_clock::now();
                 for (int t = 0; t < nt; t++) {
                     const size_t n = (*set)[t].len;
-                    if (n && std::fwrite((*set)[t].p.get(), 1, n, out) != n) die("error writing the classification output");
+                    putOut((*set)[t].p.get(), n);
                 }
                 writeBusy += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
             });
@@ -1162,7 +1205,7 @@ struct Runner {
         } else {
             for (int t = 0; t < nt; t++) {
                 const size_t n = parts[t].size();
-                if (n && std::fwrite(parts[t].data(), 1, n, out) != n) die("error writing the classification output");
+                putOut(parts[t].data(), n);
             }
         }
         lap(tm.write);
@@ -1368,7 +1411,7 @@ int run(int argc, const char **argv) {
             std::string h;
             for (size_t i = 0; i < o.colNames.size(); i++) { if (i) h.push_back('\t'); h += o.colNames[i]; }
             h.push_back('\n');
-            std::fwrite(h.data(), 1, h.size(), R.out);
+            R.putOut(h.data(), h.size());
         }
     }
 
@@ -1486,7 +1529,7 @@ int run(int argc, const char **argv) {
                 R.outRegular = ::fstat(R.outFd, &sb) == 0 && S_ISREG(sb.st_mode);
                 R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
                 R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
-                R.outMap = R.outRegular && cfamd::cf_knob("CF_CLI_MAP_OUTPUT") && std::atoi(cfamd::cf_knob("CF_CLI_MAP_OUTPUT"));
+                R.outMap = R.outRegular && cfamd::cf_knob("CF_CLI_MAP_OUTPUT") && std::atoi(cfamd::cf_knob("CF_CLI_MAP_OUTPUT")) && !o.outBgzf;
                 R.readChain.reset(); R.outChain.reset(); R.uptoReached = false;
                 const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(32u << 20);
                 void *m1 = ::mmap(nullptr, (size_t)fs1, PROT_READ, MAP_SHARED, fd1, 0), *m2 = ::mmap(nullptr, (size_t)fs2, PROT_READ, MAP_SHARED, fd2, 0);
@@ -1640,7 +1683,7 @@ int run(int argc, const char **argv) {
                 R.outRegular = ::fstat(R.outFd, &sb) == 0 && S_ISREG(sb.st_mode);
                 R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
                 R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
-                R.outMap = R.outRegular && cfamd::cf_knob("CF_CLI_MAP_OUTPUT") && std::atoi(cfamd::cf_knob("CF_CLI_MAP_OUTPUT"));
+                R.outMap = R.outRegular && cfamd::cf_knob("CF_CLI_MAP_OUTPUT") && std::atoi(cfamd::cf_knob("CF_CLI_MAP_OUTPUT")) && !o.outBgzf;
                 R.readChain.reset(); R.outChain.reset(); R.uptoReached = false;
                 const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
                 uint64_t pos = 0, idx = 0;
@@ -1926,6 +1969,12 @@ int run(int argc, const char **argv) {
                                  "read %.2f, upload + parse %.2f, host parse %.2f, enqueue %.2f, kernels + format + download %.2f, tuples %.2f, host format %.2f, write %.2f\n",
                          (unsigned long long)tb, (unsigned long long)hb, R.gts.size(), g.read, g.parse, g.hostParse, g.create, g.classify, g.report, g.format, g.write);
         }
+        if (o.outBgzf) {
+            uint64_t zt = 0, zb = 0, zn = 0; double zms = 0;
+            for (const auto &t : R.gts) { zt += t.zOutText; zb += t.zOutBytes; zn += t.zOutBatches; zms += t.zOutMs; }
+            std::fprintf(stderr, "Device deflate: %llu batch(es), %llu bytes of text into %llu bytes of BGZF members on the device, k_deflate %.2f ms in all (HIP events)\n",
+                         (unsigned long long)zn, (unsigned long long)zt, (unsigned long long)zb, zms);
+        }
         uint64_t zDev = 0;
         for (const auto &t : R.gts) zDev += t.zMembers;
         if (zDev + zHostMembers)
@@ -1935,6 +1984,11 @@ int run(int argc, const char **argv) {
                      R.indexOpenS, secs(ts), R.gts.size(), R.devs.size(), g.create, g.classify, g.results, g.report, R.tm.report, R.tm.format, R.tm.write, R.writeBusy, R.tm.produce, R.tm.wait);
     }
     R.waitWrite();
+    if (o.outBgzf) {                                  // the empty member that ends a BGZF file
+        uint8_t eof[28];
+        cf_bgzf_eof(eof);
+        if (std::fwrite(eof, 1, 28, R.out) != 28) die("error writing the classification output");
+    }
     if (R.out != stdout) { std::FILE *f = R.out; R.out = stdout; if (std::fclose(f) != 0) die("error closing the classification output"); }
     else std::fflush(stdout);
     if (!o.separator && !o.reportFile.empty()) R.writeReport(R.finishReport(), o.reportFile, hms);   // one coalesced report (centrifuge.cpp:3231-3319)

@@ -2,6 +2,7 @@
 // gfx950 only; there is no CPU path behind any compute entry point.
 #include <hip/hip_runtime.h>
 #include <sched.h>
+#include <zlib.h>
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -22,6 +23,7 @@
 #include "cf_scan.hpp"
 #include "cf_textio.hpp"
 #include "cf_inflate.hpp"
+#include "cf_deflate.hpp"
 #include "cf_restore.hpp"
 #include "cf_plan.hpp"
 #include "cf_knobs.hpp"
@@ -289,6 +291,13 @@ __global__ void __launch_bounds__(64) k_inflate_lane(DInflate d) {
     InfTables tables;
     inflate_body<1>(d, cf_global_thread(), 0, &tables);
 }
+// the formatted text deflated into BGZF members (cf_deflate.hpp): a wavefront per member, a hash table per lane in LDS — 2 x 32 KiB
+// per block, two blocks per CU: 1,024 members in flight on the chip, more than a batch of a few million rows has
+__global__ void __launch_bounds__(2 * CF_WAVE) k_deflate(DDeflate d) {
+    __shared__ uint16_t tables[2][kDefTableWords];
+    deflate_body(d, cf_global_thread() / CF_WAVE, cf_lane(), tables[threadIdx.x / CF_WAVE]);
+}
+__global__ void __launch_bounds__(256) k_deflate_compact(DDefCompact c) { def_compact_body(c, blockIdx.x, threadIdx.x, blockDim.x); }
 __global__ void k_text_cut(DTextCut c) { if (cf_global_thread() == 0) text_cut_body(c); }
 __global__ void k_text_cut_pair(DTextCutPair c) { if (cf_global_thread() == 0) text_cut_pair_body(c); }
 static_assert(kCutBadStart == kTxBadStart, "the pair cut's flag is the record pass's");
@@ -492,6 +501,14 @@ struct cf_batch {
     bool rowsStay = false;                   // cf_batch_wait_text: the rows are formatted on the device, none cross the link
     bool textDone = false;                   // ... and have been (a second wait hands the same text back: the tally is made once)
     uint64_t textBytes = 0, tupleWords = 0;
+    // cf_batch_wait_text_bgzf: the members at their stride, their sizes and places; the form the batch was waited for in
+    DevBuf<uint8_t> zOut;
+    DevBuf<uint32_t> zOutSize;
+    DevBuf<uint64_t> zOutOff;
+    bool textBgzf = false;
+    uint64_t textPlainBytes = 0;
+    hipEvent_t evDef[2] = {};                // around k_deflate (cf_batch_deflate_ms)
+    float deflateMs = 0;
     DevBuf<uint64_t> nIdx; DevBuf<uint32_t> nMsk;          // sparse N mask of the batch being uploaded
     const uint32_t *nmaskZeroOf = nullptr;                 // the mask buffer that is all zero but for the nSparsePrev words listed in nIdx
     uint64_t nSparsePrev = 0, nmaskZeroN = 0;
@@ -529,7 +546,7 @@ struct cf_batch {
     hipEvent_t ev[10] = {};                  // 0..4 stage marks of classify, 5/6 plan, 7 done, 8 uploaded, 9 classified
     hipEvent_t evLate = nullptr;             // CF_TAIL_STREAM=2: the common-case score kernel is done, the tail may start
     bool evInit = false;
-    ~cf_batch() { if (evInit) { for (auto &e : ev) (void)hipEventDestroy(e); (void)hipEventDestroy(evLate); (void)hipEventDestroy(evPostFast); (void)hipEventDestroy(evPost); } if (tail) (void)hipStreamDestroy(tail); }
+    ~cf_batch() { for (auto &e : evDef) if (e) (void)hipEventDestroy(e); if (evInit) { for (auto &e : ev) (void)hipEventDestroy(e); (void)hipEventDestroy(evLate); (void)hipEventDestroy(evPostFast); (void)hipEventDestroy(evPost); } if (tail) (void)hipStreamDestroy(tail); }
 };
 
 namespace {
@@ -2637,10 +2654,20 @@ cf_status cf_batch_set_text_skip(cf_batch *bt, uint64_t skipReads) {
 
 // The results of a batch that came as text, as text: the default columns formatted on the device from the rows the kernels left
 // there (none of them crosses the link), and the perfect multi-assignment tuples the report's EM needs beside the device's counters.
-cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) {
-    if (!bt || !res) return CF_ERR_ARG;
+static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_t *textBytes) {
+    if (!bt || !res || (bgzf && !textBytes)) return CF_ERR_ARG;
     if (bt->resultFormat != CF_RESULTS_NARROW) { g_err = "cf_batch_wait_text needs a slot whose result format is CF_RESULTS_NARROW"; return CF_ERR_ARG; }
     if (!bt->fromText) { g_err = "cf_batch_wait_text: the slot's reads did not come as text (cf_batch_upload_text): there are no readIDs on the device"; return CF_ERR_ARG; }
+    if (bt->finished && bt->textDone && bt->textBgzf != bgzf) {
+        g_err = bgzf ? "cf_batch_wait_text_bgzf: the batch was already waited for as plain text (cf_batch_wait_text)"
+                     : "cf_batch_wait_text: the batch was already waited for as BGZF members (cf_batch_wait_text_bgzf)";
+        return CF_ERR_ARG;
+    }
+    uint32_t member = kDefMember;
+    if (bgzf) {
+        if (const char *v = cfamd::cf_knob("CF_BGZF_OUT_MEMBER")) member = (uint32_t)std::strtoul(v, nullptr, 10);
+        if (!def_member_ok(member)) { g_err = "CF_BGZF_OUT_MEMBER: a multiple of 64, from 64 to 65280"; return CF_ERR_ARG; }
+    }
     const cf_status rc = guard([&] {
         cf_classifier *cl = bt->cl;
         HIP_OK(hipSetDevice(cl->ix->device));
@@ -2652,6 +2679,7 @@ cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) {
             res->tuples = bt->hTuples.p; res->n_tuple_words = bt->tupleWords;
             res->n_queries = bt->nQueries; res->total_rows = bt->rowsOut; res->planned_sa_rows = bt->rowsTotal; res->row_passes = bt->passes;
             res->slow_post = bt->hSt.p->nSlowPost; res->slow_score = bt->hSt.p->nSlowScore;
+            if (bgzf) *textBytes = bt->textPlainBytes;
             return;
         }
         makeFormatTables(cl);
@@ -2680,18 +2708,39 @@ cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) {
             f.woff = bt->woff.p; f.bases = bt->bases.p; f.nmask = bt->nmask.p; f.qualOff = bt->textFastq ? bt->txQualOff.p : nullptr;
         }
         const dim3 bl(256), gq((unsigned)std::max<uint64_t>(1, (nq + 255) / 256));
-        uint64_t total = 0;
+        uint64_t total = 0, plain = 0;
+        bt->deflateMs = 0;
         if (nq) {
             if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_size, gq, bl, 0, st, f, pc);
             else hipLaunchKernelGGL(k_fmt_size, gq, bl, 0, st, f);
             scan_enqueue<SCAN_PLAIN>(bt->txSize.p, nq, bt->txOutOff.p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
             HIP_OK(hipMemcpyAsync(bt->hTxTotal.p, bt->txOutOff.p + nq, 8, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
-            total = *bt->hTxTotal.p;
-            bt->textOut.ensure(total + 16); bt->hTextOut.ensure(total + 16);
+            total = plain = *bt->hTxTotal.p;
+            // (BGZF: the members are moved together into the room the text lay in — it has been read by then)
+            const uint64_t nMembers = bgzf ? (total + member - 1) / member : 0, room = std::max<uint64_t>(total + kInfPad, nMembers * def_stride(member));
+            bt->textOut.ensure(room);
+            bt->hTextOut.ensure((bgzf ? nMembers * def_stride(member) : total) + 16);      // (BGZF: the members' bound — no pinned memory is made between the two waits below)
             f.out = bt->textOut.p; f.outCap = total;
             if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_write, gq, bl, 0, st, f, pc);
             else hipLaunchKernelGGL(k_fmt_write, gq, bl, 0, st, f);
+            if (bgzf && nMembers) {
+                bt->zOut.ensure(nMembers * def_stride(member)); bt->zOutSize.ensure(nMembers + 16); bt->zOutOff.ensure(nMembers + 16);
+                bt->txTileA.ensure(scan_tiles_for(nMembers) + 1); bt->txTileC.ensure(scan_tiles_for(nMembers) + 1);
+                const DDeflate d{bt->textOut.p, total, member, (uint32_t)nMembers, bt->zOut.p, bt->zOutSize.p};
+                for (auto &e : bt->evDef) if (!e) HIP_OK(hipEventCreate(&e));
+                HIP_OK(hipEventRecord(bt->evDef[0], st));
+                hipLaunchKernelGGL(k_deflate, dim3((unsigned)((nMembers + 1) / 2)), dim3(2 * CF_WAVE), 0, st, d);
+                HIP_OK(hipEventRecord(bt->evDef[1], st));
+                scan_enqueue<SCAN_PLAIN>(bt->zOutSize.p, nMembers, bt->zOutOff.p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
+                const DDefCompact dc{bt->zOut.p, def_stride(member), (uint32_t)nMembers, bt->zOutSize.p, bt->zOutOff.p, bt->textOut.p};
+                hipLaunchKernelGGL(k_deflate_compact, dim3((unsigned)nMembers), dim3(256), 0, st, dc);
+                HIP_OK(hipMemcpyAsync(bt->hTxTotal.p, bt->zOutOff.p + nMembers, 8, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipStreamSynchronize(st));
+                total = *bt->hTxTotal.p;
+                if (total > nMembers * def_stride(member)) throw std::logic_error("the BGZF members outgrew their room");
+                HIP_OK(hipEventElapsedTime(&bt->deflateMs, bt->evDef[0], bt->evDef[1]));
+            } else if (bgzf) total = 0;
             HIP_OK(hipMemcpyAsync(bt->hTextOut.p, bt->textOut.p, total, hipMemcpyDeviceToHost, st));
             HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
@@ -2703,7 +2752,8 @@ cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) {
             bt->hTuples.ensure(tw);
             HIP_OK(hipMemcpy(bt->hTuples.p, bt->txTuples.p, tw * 4, hipMemcpyDeviceToHost));
         }
-        bt->textDone = true; bt->textBytes = total; bt->tupleWords = tw;
+        bt->textDone = true; bt->textBytes = total; bt->tupleWords = tw; bt->textBgzf = bgzf; bt->textPlainBytes = plain;
+        if (bgzf) *textBytes = plain;
         res->text = reinterpret_cast<const char *>(bt->hTextOut.p); res->n_bytes = total;
         res->tuples = bt->hTuples.p; res->n_tuple_words = tw;
         res->n_queries = nq; res->total_rows = bt->rowsOut; res->planned_sa_rows = bt->rowsTotal; res->row_passes = bt->passes;
@@ -2714,6 +2764,58 @@ cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) {
         bt->running = false; bt->finished = false;
     }
     return rc;
+}
+
+cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) { return waitText(bt, res, false, nullptr); }
+// ... as whole BGZF members, deflated on the device from the same text (cf_deflate.hpp): the text itself does not cross the link
+cf_status cf_batch_wait_text_bgzf(cf_batch *bt, cf_results_text *res, uint64_t *textBytes) { return waitText(bt, res, true, textBytes); }
+
+cf_status cf_batch_deflate_ms(const cf_batch *bt, float *ms) {
+    if (!bt || !ms) return CF_ERR_ARG;
+    *ms = bt->deflateMs;
+    return CF_OK;
+}
+
+// the empty member that ends a BGZF file
+void cf_bgzf_eof(uint8_t out[28]) {
+    static const uint8_t kEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::memcpy(out, kEof, 28);
+}
+// The same container from text the host holds: zlib's raw deflate at level 1, members of the same size (and knob) as the device's.
+cf_status cf_bgzf_deflate_host(const char *text, uint64_t n, void *outv, uint64_t cap, uint64_t *outBytes) {
+    if ((n && !text) || !outBytes || (cap && !outv)) return CF_ERR_ARG;
+    uint32_t member = kDefMember;
+    if (const char *v = cfamd::cf_knob("CF_BGZF_OUT_MEMBER")) member = (uint32_t)std::strtoul(v, nullptr, 10);
+    if (!def_member_ok(member)) { g_err = "CF_BGZF_OUT_MEMBER: a multiple of 64, from 64 to 65280"; return CF_ERR_ARG; }
+    uint8_t *out = static_cast<uint8_t *>(outv);
+    uint64_t at = 0;
+    std::vector<uint8_t> buf(member + 64);
+    for (uint64_t from = 0; from < n; from += member) {
+        const uint32_t len = (uint32_t)std::min<uint64_t>(member, n - from);
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(text) + from;
+        z_stream zs{};
+        if (deflateInit2(&zs, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { g_err = "cf_bgzf_deflate_host: zlib could not be set up"; return CF_ERR_NOMEM; }
+        zs.next_in = const_cast<Bytef *>(src); zs.avail_in = len;
+        zs.next_out = buf.data(); zs.avail_out = len + 5;
+        const int zr = deflate(&zs, Z_FINISH);
+        uint32_t payload = len + 5 - zs.avail_out;
+        deflateEnd(&zs);
+        if (zr != Z_STREAM_END) {                                   // longer than the stored form: stored
+            buf[0] = 1; buf[1] = (uint8_t)len; buf[2] = (uint8_t)(len >> 8); buf[3] = (uint8_t)~len; buf[4] = (uint8_t)(~len >> 8);
+            std::memcpy(buf.data() + 5, src, len);
+            payload = len + 5;
+        }
+        const uint32_t size = kDefHead + payload + kDefTail, bsize = size - 1;
+        if (at + size > cap) { g_err = "cf_bgzf_deflate_host: the output buffer is too small (cf_bgzf_deflate_host needs up to n + 31 bytes per member of text)"; return CF_ERR_ARG; }
+        const uint8_t head[kDefHead] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)bsize, (uint8_t)(bsize >> 8)};
+        std::memcpy(out + at, head, kDefHead);
+        std::memcpy(out + at + kDefHead, buf.data(), payload);
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), src, len);
+        for (uint32_t i = 0; i < 4; i++) { out[at + kDefHead + payload + i] = (uint8_t)(crc >> (8 * i)); out[at + kDefHead + payload + 4 + i] = (uint8_t)(len >> (8 * i)); }
+        at += size;
+    }
+    *outBytes = at;
+    return CF_OK;
 }
 
 cf_status cf_batch_set_limits(cf_batch *bt, uint64_t hitSlots, uint64_t rowsPerPass) {

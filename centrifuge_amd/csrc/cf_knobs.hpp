@@ -13,7 +13,8 @@
 //   builder: CF_BUILD_ROUNDS, CF_BUILD_DOUBLING          front end: CF_TEST_FAIL_OPEN, CF_TEST_FAIL_COMM (error paths of the multi-GPU driver), CF_CLI_RCCL, CF_CLI_PACKED, CF_DUMP_FROM_PACKED, CF_INGEST_BLOCK, CF_INGEST_STREAM,
 //       CF_CLI_DEVICE_TEXT (0 = the parser pool for every input), CF_CLI_TEXT_HOST_PARSE (1 = every text block through the host parser), CF_TEXT_BLOCK (bytes per text block), CF_CLI_MAP_OUTPUT,
 //       CF_CLI_DEVICE_INFLATE (0 = BGZF files are inflated by the host threads, as under --host-io)
-//   batch ABI: CF_INFLATE_LANES (1 = cf_batch_upload_bgzf inflates with the one-lane-per-member kernel: the comparison of the two forms)
+//   batch ABI: CF_INFLATE_LANES (1 = cf_batch_upload_bgzf inflates with the one-lane-per-member kernel: the comparison of the two forms),
+//       CF_BGZF_OUT_MEMBER (text bytes per member of cf_batch_wait_text_bgzf / cf_bgzf_deflate_host: a multiple of 64 from 64 to 65280, the default)
 #pragma once
 #include <cstdlib>
 

@@ -388,6 +388,23 @@ typedef struct {
     uint32_t row_passes, slow_post, slow_score;
 } cf_results_text;
 cf_status cf_batch_wait_text(cf_batch *, cf_results_text *out);
+/* The same, compressed: everything cf_batch_wait_text does (preconditions, tally, tuples, counters, column program), but out->text /
+ * out->n_bytes are whole BGZF members (the blocked gzip of htslib's bgzf.c; what stands beside the reference's output stage,
+ * AlnSinkSam::appendMate into the OutputQueue, is a `| bgzip` behind it), deflated ON THE DEVICE from the formatted text — one
+ * wavefront per member of 65,280 text bytes, fixed-Huffman or stored blocks — so that the text itself never crosses the link.
+ * Inflated one after the other the members are byte for byte the text cf_batch_wait_text would have returned; *text_bytes is its
+ * size.  A batch of no queries gives no member (n_bytes 0); a second call returns the same bytes; a batch is waited for in ONE
+ * form: after either call the other one is CF_ERR_ARG (cf_last_error says so).  A file of such members ends with cf_bgzf_eof. */
+cf_status cf_batch_wait_text_bgzf(cf_batch *, cf_results_text *out, uint64_t *text_bytes);
+/* the device time of the deflate kernel of the slot's last cf_batch_wait_text_bgzf (HIP events around it on the slot's stream; 0:
+ * the batch held no rows), like cf_batch_plan_ms */
+cf_status cf_batch_deflate_ms(const cf_batch *, float *ms);
+/* the empty member that ends a BGZF file (28 bytes) */
+void      cf_bgzf_eof(uint8_t out[28]);
+/* The same container made on the host — zlib's raw deflate at level 1, members of the same size — for text the host formatted
+ * (the header line, the rows of OutputQueue's host-side stand-in).  The compressed bytes are not the device's; what they inflate to
+ * is.  cap: the room at out (n + 31 bytes per started 65,280 bytes of text always suffice); too little: CF_ERR_ARG. */
+cf_status cf_bgzf_deflate_host(const char *text, uint64_t n, void *out, uint64_t cap, uint64_t *out_bytes);
 /* Which columns cf_batch_wait_text prints: any list --tab-fmt-cols / --out-fmt sam can name (centrifuge.cpp:484-520), formatted
  * on the device like the default eight — taxRank / taxName from per-taxon string tables made at the first program that names
  * them, readSeq* from the batch's packed words as A C G T N (never copied from the uploaded text, which may be wrapped or lower

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end wall time of the centrifuge-class front ends (ours vs the reference binary) on one
-FASTA file: index built by the GPU builder, reads sampled from the genomes."""
+FASTA file: index built by the GPU builder, reads sampled from the genomes.
+usage: cli_e2e.py <genomes> <genome length> <reads> [noref | outbgzf [other centrifuge-class]]   (outbgzf: our plain output against
+--out-bgzf, another build's plain run beside them, and gzip -1 of the TSV on 16 cores)"""
 import os
 import subprocess
 import sys
@@ -34,6 +36,36 @@ def main():
     bench.write_fasta(os.path.join(d, "reads.fa"), bench.read_names(n), codes)
     ours = os.path.join(ROOT, "centrifuge_amd", "bin", "centrifuge-class")
     ref = os.path.join(O.REF_DIR, "centrifuge-class")
+    if len(sys.argv) > 4 and sys.argv[4] == "outbgzf":
+        # the plain output against --out-bgzf (rows deflated on the device), three runs of each in turn: whole process, the -t lines
+        # (search phase, k_deflate's HIP-event time), the output's bytes = what crosses the link for the rows; then, with a fifth
+        # argument, another build's binary (the parent commit's) on the same job; then the plain TSV through gzip -1 on 16 cores
+        import shutil
+        keep = ("ime", "search", "Device text", "Device deflate")
+        forms = [("plain", ours, []), ("out-bgzf", ours, ["--out-bgzf"])] + ([("parent", sys.argv[5], [])] if len(sys.argv) > 5 else [])
+        for tag, exe, extra in forms * 3:
+            out = os.path.join(d, tag + ".out")
+            t0 = time.time()
+            r = subprocess.run([exe, "-f", "-t", "-p", "8", "-x", os.path.join(d, "idx"), "-U", os.path.join(d, "reads.fa"), "-S", out,
+                                "--report-file", os.path.join(d, tag + ".rep")] + extra, capture_output=True, text=True)
+            dt = time.time() - t0
+            print("%-9s wall %.2fs -> %.3g reads/s  rc=%d  output %d bytes (%.1f per read) | %s" % (tag, dt, n / dt, r.returncode, os.path.getsize(out), os.path.getsize(out) / n,
+                  " ; ".join(l for l in r.stderr.splitlines() if any(k in l for k in keep))), flush=True)
+        same = subprocess.run("gzip -dc %s | cmp - %s" % (os.path.join(d, "out-bgzf.out"), os.path.join(d, "plain.out")), shell=True).returncode == 0
+        print("inflated output identical to the plain one: %s" % same, flush=True)
+        if shutil.which("gzip") and shutil.which("split"):
+            parts = os.path.join(d, "parts")
+            shutil.rmtree(parts, ignore_errors=True)
+            os.makedirs(parts)
+            t0 = time.time()
+            subprocess.check_call(["split", "-n", "l/16", os.path.join(d, "plain.out"), os.path.join(parts, "p")])
+            t1 = time.time()
+            ps = [subprocess.Popen(["gzip", "-1", os.path.join(parts, f)]) for f in sorted(os.listdir(parts))]
+            ok = all(p.wait() == 0 for p in ps)
+            size = sum(os.path.getsize(os.path.join(parts, f)) for f in os.listdir(parts))
+            print("gzip -1 of the plain TSV in 16 pieces at once: split %.2fs + gzip %.2fs, %d bytes (%.1f per read) ok=%s" % (t1 - t0, time.time() - t1, size, size / n, ok), flush=True)
+            shutil.rmtree(parts, ignore_errors=True)
+        return
     noref = len(sys.argv) > 4 and sys.argv[4] == "noref"
     runs = [("ours -p 8", ours, 8), ("ours -p 1", ours, 1)] + ([] if noref else [("reference -p 8", ref, 8)])
     for tag, exe, p in runs:
