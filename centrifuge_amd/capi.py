@@ -159,6 +159,7 @@ EXPORTS = [
     "cf_report_adopt_counts", "cf_debug_scan", "cf_host_alloc", "cf_host_free", "cf_batch_alloc", "cf_batch_upload_packed_async", "cf_classify_async", "cf_batch_download_async",
     "cf_batch_submit", "cf_batch_wait", "cf_batch_upload", "cf_batch_set_limits", "cf_batch_upload_bgzf", "cf_batch_upload_bgzf_pair",
     "cf_batch_wait_text_bgzf", "cf_batch_deflate_ms", "cf_bgzf_eof", "cf_bgzf_deflate_host",
+    "cf_kreport_enable", "cf_kreport_reset", "cf_kreport_get", "cf_kreport_write", "cf_batch_kreport_ms", "cf_batch_text_names",
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
 ]
@@ -249,6 +250,8 @@ def lib():
         "cf_batch_wait_text": (i32, [vp, C.POINTER(ResultsText)]),
         "cf_batch_wait_text_bgzf": (i32, [vp, C.POINTER(ResultsText), C.POINTER(u64)]),
         "cf_batch_deflate_ms": (i32, [vp, C.POINTER(C.c_float)]),
+        "cf_kreport_enable": (i32, [vp]), "cf_kreport_reset": (i32, [vp]), "cf_kreport_get": (i32, [vp, vp, vp]),
+        "cf_kreport_write": (i32, [vp, vp, C.c_uint64, C.c_char_p]), "cf_batch_kreport_ms": (i32, [vp, C.POINTER(C.c_float)]), "cf_batch_text_names": (i32, [vp, vp]),
         "cf_bgzf_eof": (None, [vp]), "cf_bgzf_deflate_host": (i32, [cp, u64, vp, u64, C.POINTER(u64)]),
         "cf_text_column_of": (C.c_int32, [cp]), "cf_batch_set_text_columns": (i32, [vp, vp, u32]),
         "cf_batch_set_text_trim": (i32, [vp, u32, u32]), "cf_batch_set_text_skip": (i32, [vp, u64]),
@@ -426,6 +429,27 @@ class Classifier:
         a = np.zeros(n, dtype=np.uint64)
         _check(self.L.cf_counts_get_single(self.h, a.ctypes.data))
         return a
+
+    def enable_kreport(self):
+        """from now on every batch of this classifier is tallied for the Kraken-style report (cf_kreport_enable)"""
+        _check(self.L.cf_kreport_enable(self.h))
+
+    def reset_kreport(self):
+        _check(self.L.cf_kreport_reset(self.h))
+
+    def kreport_counts(self):
+        """reads per LCA taxon (dense order, taxon 0 = unclassified) and the number of reads counted (cf_kreport_get)"""
+        a = np.zeros(self.index.num_taxa, dtype=np.uint64)
+        n = C.c_uint64(0)
+        _check(self.L.cf_kreport_get(self.h, a.ctypes.data, C.addressof(n)))
+        return a, int(n.value)
+
+    def write_kreport(self, path, counts=None):
+        """what centrifuge-kreport prints for the reads tallied so far, to `path` (cf_kreport_write); counts: a
+        (per_taxon, n_reads) pair summed over several classifiers instead of this one's"""
+        a, n = counts if counts is not None else self.kreport_counts()
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        _check(self.L.cf_kreport_write(self.index.h, a.ctypes.data, int(n), os.fsencode(path)))
 
     def allreduce_counts(self, nccl_comm, stream=None):
         """in-place RCCL sum of the device counters over the communicator's ranks"""
@@ -727,6 +751,12 @@ class Slot:
         tuples = np.frombuffer(C.string_at(r.tuples, 4 * r.n_tuple_words), dtype=np.uint32).copy() if r.n_tuple_words else np.zeros(0, np.uint32)
         return members, n.value, tuples, {"n_queries": r.n_queries, "total_rows": r.total_rows, "planned_sa_rows": r.planned_sa_rows, "row_passes": r.row_passes,
                                           "slow_post": r.slow_post, "slow_score": r.slow_score}
+
+    def kreport_ms(self):
+        """k_kreport's time in the slot's last batch (cf_batch_kreport_ms)"""
+        ms = C.c_float(0)
+        _check(self.L.cf_batch_kreport_ms(self.h, C.byref(ms)))
+        return float(ms.value)
 
     def deflate_ms(self):
         """device ms of the deflate kernel of the last wait_text_bgzf()"""

@@ -55,6 +55,7 @@ struct Opts {
     int slots = 2;                                      // --slots: GPU threads (batch slots, each with its stream) per device
     bool slotsSet = false;
     int devInflate = 1;                                 // --device-inflate off | unpaired | all: which BGZF inputs are inflated on the device (0, 1, 2)
+    std::string kreportFile;                            // --kreport-file: what centrifuge-kreport prints for this run's output, tallied on the device (cf_kreport_enable)
     bool outBgzf = false;                               // --out-bgzf: the classification output is one BGZF file (the device text path's blocks are deflated on the device)
     bool hostIo = false;                                // --host-io: the parser pool and the formatter threads for every input (no device text path)
     int smallRangeRows = 0;                             // --small-range-rows: cf_index_options::small_range_rows (0 = automatic, -1 = off)
@@ -96,6 +97,8 @@ void usage(std::FILE *f) {
         " Classification:  -k <int> (5)  --min-hitlen <int> (22)  --host-taxids <t,..>  --exclude-taxids <t,..>\n"
         "          --classification-rank <strain|species|genus|family|order|class|phylum>  --no-traverse\n"
         " Output:  -S <file>  --report-file <file> (centrifuge_report.tsv)  --no-abundance  --tab-fmt-cols <c,..>  --out-fmt tab|sam  -t/--time\n"
+        "          --kreport-file <file> (the Kraken-style report `centrifuge-kreport -x <cf-idx> <output>` prints for this run's output, tallied on\n"
+        "             the device: no second pass over the text.  Two neighbouring reads of one name are refused: exit status 1, no file)\n"
         "          --out-bgzf (the classification output — -S or stdout: header line, rows, --separator markers, the SAM form — as one BGZF\n"
         "          file, the blocked gzip of bgzip / htslib, that inflates to the bytes the run prints without the flag; rows formatted on\n"
         "          the device are deflated there and cross the link compressed, the rest is deflated by zlib; the report stays plain)\n"
@@ -200,6 +203,7 @@ Opts parse(int argc, const char **argv) {
         else if (a == "--slots") { o.slots = std::atoi(val().c_str()); o.slotsSet = true; if (o.slots < 1) die("--slots arg must be at least 1"); }
         else if (a == "--host-io") o.hostIo = true;
         else if (a == "--out-bgzf") o.outBgzf = true;
+        else if (a == "--kreport-file") o.kreportFile = val();
         else if (a == "--device-inflate") {
             const std::string m = val();
             if (m == "off") o.devInflate = 0; else if (m == "unpaired") o.devInflate = 1; else if (m == "all") o.devInflate = 2;
@@ -415,6 +419,8 @@ struct GpuThread {
     std::string zHead2;                             // ... of the second file of mates
     std::string tabText;                            // a tabbed block parsed on the host: the text of its runs of pairs / unpaired reads, one behind the other
     std::vector<char> zText;                        // --out-bgzf: a block the host formatted, deflated (cf_bgzf_deflate_host)
+    double krMs = 0;                                // --kreport-file: k_kreport's ms over this thread's batches (HIP events)
+    uint64_t krBatches = 0;
     uint64_t zOutText = 0, zOutBytes = 0, zOutBatches = 0;   // ... and the batches deflated on the device: their text, their members, k_deflate's ms
     double zOutMs = 0;
 };
@@ -657,6 +663,7 @@ struct Runner {
             CF_TRY(cf_batch_wait_narrow(g.slot, &res));
             lap(g.tm.classify);
             b.nq = res.n_queries;
+            krHost(b, g, 0, b.paired);
             b.narrowRows = defaultCols;
             if (b.narrowRows) {
                 // the default columns are formatted straight from the narrow rows: out of the slot's pinned memory as they are
@@ -683,6 +690,7 @@ struct Runner {
             CF_TRY(cf_batch_wait(g.slot, &res));
             lap(g.tm.classify);
             b.nq = res.n_queries;
+            krHost(b, g, 0, b.paired);
             // a recycled batch keeps its (already mapped) buffers
             if (b.rows.size() < res.total_rows) b.rows.resize(res.total_rows);
             if (b.nRows.size() < b.nq) b.nRows.resize(b.nq);
@@ -697,6 +705,73 @@ struct Runner {
         }
         lap(g.tm.results);
         if (g.rep) { CF_TRY(cf_report_add(g.rep, b.rows.data(), b.nRows.data(), b.maxScore.data(), b.nq, 0)); lap(g.tm.report); }
+    }
+
+    // --kreport-file: centrifuge-kreport merges neighbouring rows of equal readID, the device's tally counts reads — so two
+    // neighbouring reads of one name have to be found and refused.  Every printed piece of the run (a batch, or a run of a tabbed
+    // block) leaves its first and last readID here under its place in the output (the batch's number, the run's within it); pairs
+    // inside a piece are found where it is parsed — on the device (cf_batch_text_names) or here from the names (krHost) —, pairs
+    // across two pieces at the end (krFinish).  Names longer than 255 bytes count as equal when their lengths and those bytes agree.
+    struct KrPiece { uint64_t seq, sub; uint32_t firstLen, lastLen; std::string first, last; };
+    std::mutex krMu;
+    std::vector<KrPiece> krPieces;
+    bool krDupFound = false;
+    uint64_t krDupSeq = 0, krDupSub = 0;
+    std::string krDupName;
+    void krNote(uint64_t seq, uint64_t sub, const char *name, size_t n) {            // (the pair that comes first in the output is named)
+        if (krDupFound && std::make_pair(krDupSeq, krDupSub) <= std::make_pair(seq, sub)) return;
+        krDupFound = true; krDupSeq = seq; krDupSub = sub; krDupName.assign(name, std::min<size_t>(n, 255));
+    }
+    void krTime(GpuThread &g) {
+        float ms = 0;
+        CF_TRY(cf_batch_kreport_ms(g.slot, &ms));
+        g.krMs += ms; g.krBatches++;
+    }
+    static size_t readIdLen(const char *name, size_t n) {                             // appendReadId's span
+        if (n >= 2 && name[n - 2] == '/' && (name[n - 1] == '1' || name[n - 1] == '2' || name[n - 1] == '3')) n -= 2;
+        size_t i = 0;
+        while (i < n && !std::isspace((unsigned char)name[i])) i++;
+        return i;
+    }
+    // a batch whose rows were formatted on the device
+    void krDevice(const Batch &b, GpuThread &g) {
+        if (o.kreportFile.empty()) return;
+        krTime(g);
+        cf_text_names tn;
+        CF_TRY(cf_batch_text_names(g.slot, &tn));
+        std::lock_guard<std::mutex> lk(krMu);
+        krPieces.push_back({b.seq, 0, tn.first_len, tn.last_len, std::string(tn.first, std::min<uint32_t>(tn.first_len, 255)), std::string(tn.last, std::min<uint32_t>(tn.last_len, 255))});
+        if (tn.n_dup) krNote(b.seq, 0, tn.dup, tn.dup_len);
+    }
+    // the reads of b.r, parsed on the host: query q prints the readID of read q (mates: of read 2q)
+    void krHost(const Batch &b, GpuThread &g, uint64_t sub, bool paired) {
+        if (o.kreportFile.empty()) return;
+        krTime(g);
+        const ReadSoA &r = b.r;
+        const size_t step = paired ? 2 : 1, n = r.size() / step;
+        if (!n) return;
+        const char *prev = nullptr, *first = nullptr, *dup = nullptr;
+        size_t prevLen = 0, firstLen = 0, dupLen = 0;
+        for (size_t q = 0; q < n; q++) {
+            const char *nm = r.names.data() + r.nameOff[q * step];
+            const size_t len = readIdLen(nm, (size_t)(r.nameOff[q * step + 1] - r.nameOff[q * step]));
+            if (q == 0) { first = nm; firstLen = len; }
+            else if (!dup && len == prevLen && std::memcmp(nm, prev, len) == 0) { dup = nm; dupLen = len; }
+            prev = nm; prevLen = len;
+        }
+        std::lock_guard<std::mutex> lk(krMu);
+        krPieces.push_back({b.seq, sub, (uint32_t)firstLen, (uint32_t)prevLen, std::string(first, std::min<size_t>(firstLen, 255)), std::string(prev, std::min<size_t>(prevLen, 255))});
+        if (dup) krNote(b.seq, sub, dup, dupLen);
+    }
+    // the pieces in output order: true when two neighbouring reads of the run carry one name (name: the first such)
+    bool krFinish(std::string &name) {
+        std::sort(krPieces.begin(), krPieces.end(), [](const KrPiece &a, const KrPiece &b) { return std::make_pair(a.seq, a.sub) < std::make_pair(b.seq, b.sub); });
+        for (size_t i = 1; i < krPieces.size(); i++) {
+            const KrPiece &a = krPieces[i - 1], &b = krPieces[i];
+            if (a.lastLen == b.firstLen && a.last == b.first) { krNote(b.seq, b.sub, b.first.data(), b.first.size()); break; }      // (a pair inside an earlier piece stays the one named)
+        }
+        name = krDupName;
+        return krDupFound;
     }
 
     static void writeAll(int fd, const char *p, size_t n, bool positioned, uint64_t at) {
@@ -848,6 +923,7 @@ struct Runner {
             } else CF_TRY(cf_batch_wait_text(g.slot, &res));
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
+            krDevice(b, g);
             text = res.text; nText = res.n_bytes;
             b.nq = res.n_queries;
             textBatches++; g.textBlocks++;
@@ -871,6 +947,7 @@ struct Runner {
                 for (uint64_t i = drop; i < drop + take; i++) { one(src, i); if (mates) one(b.r2, i); }
             }
             // the reads of b.r through the kernels and the host formatter: their text into this thread's buffer
+            uint64_t krSub = 0;
             auto hostRun = [&](bool mates) {
             b.r.pack();
             b.paired = mates;
@@ -887,6 +964,7 @@ struct Runner {
             CF_TRY(cf_batch_wait_narrow(g.slot, &res));
             lap(g.tm.classify);
             b.nq = res.n_queries;
+            krHost(b, g, krSub++, mates);
             b.narrowRows = true;
             if (b.rows16.size() < res.total_rows) b.rows16.resize(res.total_rows);
             if (b.qinfo.size() < b.nq) b.qinfo.resize(b.nq);
@@ -1022,6 +1100,7 @@ struct Runner {
             } else CF_TRY(cf_batch_wait_text(g.slot, &res));
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
+            krDevice(b, g);
             text = res.text; nText = res.n_bytes;
             textBatches++; g.textBlocks++;
             lap(g.tm.report);
@@ -1111,6 +1190,7 @@ struct Runner {
             } else CF_TRY(cf_batch_wait_text(g.slot, &res));
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
+            krDevice(b, g);
             text = res.text; nText = res.n_bytes;
             textBatches++; g.textBlocks++;
             lap(g.tm.report);
@@ -1376,6 +1456,8 @@ int run(int argc, const char **argv) {
         p.host_taxids = o.hostTaxids.data(); p.n_host = (int32_t)o.hostTaxids.size();
         p.exclude_taxids = o.excludeTaxids.data(); p.n_exclude = (int32_t)o.excludeTaxids.size();
         for (auto &d : R.devs) CF_TRY(cf_classifier_create(d.ix, &p, &d.clf));
+        if (!o.kreportFile.empty())
+            for (auto &d : R.devs) if (cf_kreport_enable(d.clf) != CF_OK) die(std::string("Error: --kreport-file: ") + cf_last_error());
         // The device text path (round 6): whole blocks of a plain FASTA / FASTQ file up as text, the rows back as text — with
         // -5 / -3 as the record pass's window (cf_batch_set_text_trim), -s / -u by the block (cf_batch_set_text_skip, max_reads), up to CF_TEXT_MAX_COLS columns (cf_batch_set_text_columns), -k <= 63 (the narrow rows' six bits).  Every GPU thread
         // then also reads its blocks and writes its text, so there are more of them (each with a slot on the device).
@@ -1975,6 +2057,11 @@ int run(int argc, const char **argv) {
             std::fprintf(stderr, "Device deflate: %llu batch(es), %llu bytes of text into %llu bytes of BGZF members on the device, k_deflate %.2f ms in all (HIP events)\n",
                          (unsigned long long)zn, (unsigned long long)zt, (unsigned long long)zb, zms);
         }
+        if (!o.kreportFile.empty()) {
+            double ms = 0; uint64_t nb = 0;
+            for (const auto &t : R.gts) { ms += t.krMs; nb += t.krBatches; }
+            std::fprintf(stderr, "Kraken-style tally: %llu batch(es), k_kreport %.3f ms in all, %.4f ms per batch (HIP events)\n", (unsigned long long)nb, ms, nb ? ms / (double)nb : 0.0);
+        }
         uint64_t zDev = 0;
         for (const auto &t : R.gts) zDev += t.zMembers;
         if (zDev + zHostMembers)
@@ -1992,11 +2079,33 @@ int run(int argc, const char **argv) {
     if (R.out != stdout) { std::FILE *f = R.out; R.out = stdout; if (std::fclose(f) != 0) die("error closing the classification output"); }
     else std::fflush(stdout);
     if (!o.separator && !o.reportFile.empty()) R.writeReport(R.finishReport(), o.reportFile, hms);   // one coalesced report (centrifuge.cpp:3231-3319)
+    int rc = 0;
+    if (!o.kreportFile.empty()) {
+        std::string name;
+        if (R.krFinish(name)) {
+            std::fprintf(stderr, "Error: --kreport-file: two neighbouring reads are both named '%s'; centrifuge-kreport counts them as one read and the device's tally as two, so %s is not written: "
+                                 "run centrifuge-kreport on the classification output instead\n", name.c_str(), o.kreportFile.c_str());
+            rc = 1;
+        } else {
+            const auto k0 = std::chrono::steady_clock::now();
+            const uint64_t nTaxa = cf_index_num_taxa(R.ix);
+            std::vector<uint64_t> sum(nTaxa, 0), one(nTaxa);
+            uint64_t nReads = 0;
+            for (auto &d : R.devs) {                                // (the devices' counters are summed here: no collective)
+                uint64_t n = 0;
+                CF_TRY(cf_kreport_get(d.clf, one.data(), &n));
+                for (uint64_t i = 0; i < nTaxa; i++) sum[i] += one[i];
+                nReads += n;
+            }
+            CF_TRY(cf_kreport_write(R.ix, sum.data(), nReads, o.kreportFile.c_str()));
+            if (o.timing) std::fprintf(stderr, "Kraken-style report %s: %llu reads, written in %.3f s\n", o.kreportFile.c_str(), (unsigned long long)nReads, secs(k0));
+        }
+    }
     if (o.timing) {
         std::fprintf(stderr, "Overall time: %s\n", hms(secs(t0)).c_str());
         std::fprintf(stderr, "Overall seconds: %.2f (from the start of the call to here; of which before the index open %.2f)\n", secs(t0), R.beforeOpenS);
     }
-    return 0;
+    return rc;
 }
 
 }  // namespace

@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <chrono>
 #include <cstdio>
@@ -20,6 +21,7 @@
 #include "../../include/centrifuge_amd.h"
 #include "cf_index.hpp"
 #include "cf_kernels.hpp"
+#include "cf_kreport_tree.hpp"
 #include "cf_scan.hpp"
 #include "cf_textio.hpp"
 #include "cf_inflate.hpp"
@@ -265,6 +267,11 @@ __global__ void __launch_bounds__(1024) k_count(DBatch b, uint32_t slotBits, boo
     __shared__ uint32_t slots[3 * kCountSlots];
     count_body(b, slots, blockIdx.x, slotBits, direct);
 }
+// the Kraken-style report's tally of a pass (kreport_body): k_count's grid and block, two thirds of its LDS
+__global__ void __launch_bounds__(1024) k_kreport(DBatch b, DKreport kr, uint32_t slotBits, bool direct) {
+    __shared__ uint32_t slots[2 * kCountSlots + 1];
+    kreport_body(b, kr, slots, blockIdx.x, slotBits, direct);
+}
 __global__ void __launch_bounds__(256) k_plan(DPlan p) { plan_body(p, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_plan_fill(DPlan p) { plan_fill_body(p, cf_global_thread()); }
 // the forward strands' words in search order (rev_word), one thread per (read, word): neighbouring lanes read and write neighbouring words
@@ -278,6 +285,8 @@ __global__ void __launch_bounds__(256) k_compact(DCompact c) {
 // the text forms (cf_textio.hpp): ingest and egress of the front end on the device, one thread per piece / record / query
 __global__ void __launch_bounds__(256) k_text_count(DTextMark m) { text_count_body(m, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void __launch_bounds__(256) k_text_mark(DTextMark m) { text_mark_body(m, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ void __launch_bounds__(256) k_text_dup(DTextDup d) { text_dup_body(d, cf_global_thread()); }
+__global__ void k_text_dup_name(DTextDup d) { if (cf_global_thread() == 0) text_dup_name_body(d); }
 __global__ void __launch_bounds__(256) k_text_records(DTextRec d) { text_record_body_t<false>(d, cf_global_thread()); }
 // (the tabbed formats: an instantiation of their own, so that the FASTA / FASTQ pass keeps its registers)
 __global__ void __launch_bounds__(256) k_text_records_tab(DTextRec d) { text_record_body_t<true>(d, cf_global_thread()); }
@@ -412,6 +421,10 @@ struct cf_classifier {
     DevBuf<uint8_t> refExcluded;
     DevBuf<uint64_t> hostSet;
     DevBuf<unsigned long long> counts;           // per taxon: reads, unique reads (count_body), perfect single assignments (fmt_write_body)
+    // cf_kreport_enable: the tree for lca_body, reads per LCA taxon + their total (kreport_body) — apart from `counts` and its all-reduce
+    DevBuf<uint64_t> lcaTab;
+    DevBuf<unsigned long long> kreportCounts;
+    bool kreportOn = false;
     // the strings a formatted row repeats (cf_batch_wait_text), made at the first use
     DevBuf<uint8_t> fmtStrs, fmtLeaf;
     DevBuf<uint32_t> fmtUidOff, fmtRankOff, fmtTaxOff;
@@ -482,6 +495,9 @@ struct cf_batch {
     bool textFastq = false;                  // the block that is loaded is FASTQ (txQualOff holds its quality lines' places)
     DevBuf<uint64_t> txBase, txOutOff, txTileA;
     DevBuf<TextStatus> txSt;
+    DevBuf<TextNames> txNames;               // with the Kraken-style tally on: text_dup_body's findings (cf_batch_text_names)
+    PinBuf<TextNames> hTxNames;
+    bool namesValid = false;
     PinBuf<TextStatus> hTxSt;
     PinBuf<uint64_t> hTxTotal;
     PinBuf<uint8_t> hTextOut;
@@ -509,6 +525,9 @@ struct cf_batch {
     uint64_t textPlainBytes = 0;
     hipEvent_t evDef[2] = {};                // around k_deflate (cf_batch_deflate_ms)
     float deflateMs = 0;
+    hipEvent_t evKr[2] = {};                 // around k_kreport of a batch's first pass (cf_batch_kreport_ms)
+    bool krTimed = false;
+    float kreportMs = 0;
     DevBuf<uint64_t> nIdx; DevBuf<uint32_t> nMsk;          // sparse N mask of the batch being uploaded
     const uint32_t *nmaskZeroOf = nullptr;                 // the mask buffer that is all zero but for the nSparsePrev words listed in nIdx
     uint64_t nSparsePrev = 0, nmaskZeroN = 0;
@@ -546,7 +565,7 @@ struct cf_batch {
     hipEvent_t ev[10] = {};                  // 0..4 stage marks of classify, 5/6 plan, 7 done, 8 uploaded, 9 classified
     hipEvent_t evLate = nullptr;             // CF_TAIL_STREAM=2: the common-case score kernel is done, the tail may start
     bool evInit = false;
-    ~cf_batch() { for (auto &e : evDef) if (e) (void)hipEventDestroy(e); if (evInit) { for (auto &e : ev) (void)hipEventDestroy(e); (void)hipEventDestroy(evLate); (void)hipEventDestroy(evPostFast); (void)hipEventDestroy(evPost); } if (tail) (void)hipStreamDestroy(tail); }
+    ~cf_batch() { for (auto &e : evDef) if (e) (void)hipEventDestroy(e); for (auto &e : evKr) if (e) (void)hipEventDestroy(e); if (evInit) { for (auto &e : ev) (void)hipEventDestroy(e); (void)hipEventDestroy(evLate); (void)hipEventDestroy(evPostFast); (void)hipEventDestroy(evPost); } if (tail) (void)hipStreamDestroy(tail); }
 };
 
 namespace {
@@ -1585,6 +1604,7 @@ static void sizeBatch(cf_batch *bt, uint64_t nReads, uint64_t nWords, uint64_t n
     bt->rowsSpec = std::min<uint64_t>(bt->rowsSpec, nq * (uint64_t)cl->d.k);
     bt->hRows.ensure(std::max<uint64_t>(bt->rowsSpec, nq + nq / 4 + 1024));
     if (g_dryBytes) return;
+    if (cl->kreportOn) for (auto &e : bt->evKr) if (!e) HIP_OK(hipEventCreate(&e));
     if (!bt->evInit) { for (auto &e : bt->ev) HIP_OK(hipEventCreate(&e)); HIP_OK(hipEventCreate(&bt->evLate)); HIP_OK(hipEventCreate(&bt->evPostFast)); HIP_OK(hipEventCreate(&bt->evPost)); bt->evInit = true; }
     // the slot's own stream: the general post kernel runs on it beside the early score kernel (enqueueClassify; CF_EARLY_SCORE=0: not),
     // and the CF_TAIL_STREAM experiments
@@ -1751,6 +1771,14 @@ static bool enqueueRowPass(cf_batch *bt, uint32_t qLo, hipStream_t st, bool mark
         hipLaunchKernelGGL(k_score, listGrid(ix, nq), dim3(64), (size_t)(64 / sparse) * score_scratch_bytes(capRows), st, ix.d, cl->d, d, capRows, capRows ? sparse : 1u, 0u, 0xffffffffu);
         static const uint32_t slotBits = (uint32_t)std::clamp(envInt("CF_COUNT_SLOT_BITS", (int)kCountSlotBits), 1, (int)kCountSlotBits);   // (tests: few slots = probing, overflow)
         hipLaunchKernelGGL(k_count, dim3((nq + kCountChunk - 1) / kCountChunk), dim3(1024), 0, st, d, slotBits, d.nTaxa <= (1u << slotBits));
+        if (cl->kreportOn) {
+            const bool timed = marks && bt->evKr[0];
+            if (timed) HIP_OK(hipEventRecord(bt->evKr[0], st));
+            const DKreport kr{cl->lcaTab.p, cl->kreportCounts.p, (uint32_t)cl->d.k, kCountChunk};
+            hipLaunchKernelGGL(k_kreport, dim3((nq + kCountChunk - 1) / kCountChunk), dim3(1024), 0, st, d, kr, slotBits, d.nTaxa <= (1u << slotBits));
+            if (timed) HIP_OK(hipEventRecord(bt->evKr[1], st));
+            if (timed) bt->krTimed = true;
+        }
     }
     if (marks) HIP_OK(hipEventRecord(bt->ev[4], st));
     return counted;
@@ -1770,6 +1798,7 @@ static void enqueueCompact(cf_batch *bt, hipStream_t st) {
 
 static void enqueueClassify(cf_batch *bt, hipStream_t st) {
     cf_classifier *cl = bt->cl;
+    bt->krTimed = false;
     HIP_OK(hipMemsetAsync(bt->cursor.p, 0, 32, st));
     HIP_OK(hipMemsetAsync(bt->ops.p, 0, sizeof(OpCounts), st));
     // (qRows: every query's entry is written by one of the post kernels; nOut: by one of the score kernels — queries outside
@@ -1851,6 +1880,8 @@ static void waitBatch(cf_batch *bt) {
     HIP_OK(hipEventSynchronize(bt->ev[9]));
     auto lapse = [&](float &ms, int a, int b) { if (hipEventElapsedTime(&ms, bt->ev[a], bt->ev[b]) != hipSuccess) { ms = 0; (void)hipGetLastError(); } };
     lapse(bt->planMs, 5, 6);
+    bt->kreportMs = 0;
+    if (bt->krTimed && hipEventElapsedTime(&bt->kreportMs, bt->evKr[0], bt->evKr[1]) != hipSuccess) { bt->kreportMs = 0; (void)hipGetLastError(); }
     lapse(bt->ms[0], 0, 1); lapse(bt->ms[1], 1, 2); lapse(bt->ms[2], 2, 3); lapse(bt->ms[3], 3, 4); lapse(bt->ms[4], 0, 4);
     if (bt->hSt.p->flags & kStLenOverflow) throw ArgError("a read is longer than the max_len the batch was submitted with");
     if (bt->hSt.p->flags & kStWordsOverflow) throw ArgError("the read lengths need more packed words than n_words says were uploaded");
@@ -2709,6 +2740,19 @@ static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_
         }
         const dim3 bl(256), gq((unsigned)std::max<uint64_t>(1, (nq + 255) / 256));
         uint64_t total = 0, plain = 0;
+        bt->namesValid = false;
+        if (cl->kreportOn) {                                   // the readIDs that repeat their predecessor's, the batch's first and last
+            bt->txNames.ensure(1); bt->hTxNames.ensure(1);
+            std::memset(bt->hTxNames.p, 0, sizeof(TextNames));
+            if (nq) {
+                HIP_OK(hipMemsetAsync(bt->txNames.p, 0, sizeof(TextNames), st));
+                const DTextDup dd{bt->text.p, bt->txIdOff.p, bt->txIdLen.p, (uint32_t)nq, (uint32_t)bt->paired, bt->txSt.p, bt->txNames.p};
+                hipLaunchKernelGGL(k_text_dup, gq, bl, 0, st, dd);
+                hipLaunchKernelGGL(k_text_dup_name, dim3(1), dim3(64), 0, st, dd);
+                HIP_OK(hipMemcpyAsync(bt->hTxNames.p, bt->txNames.p, sizeof(TextNames), hipMemcpyDeviceToHost, st));
+            }
+            bt->namesValid = true;
+        }
         bt->deflateMs = 0;
         if (nq) {
             if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_size, gq, bl, 0, st, f, pc);
@@ -2977,6 +3021,67 @@ cf_status cf_counts_get(cf_classifier *cl, uint64_t *nReads, uint64_t *nUnique) 
         HIP_OK(hipMemcpy(nReads, cl->counts.p, n * 8, hipMemcpyDeviceToHost));
         HIP_OK(hipMemcpy(nUnique, cl->counts.p + n, n * 8, hipMemcpyDeviceToHost));
     });
+}
+// ---- the Kraken-style report's tally (kreport_body): see centrifuge_amd.h
+cf_status cf_kreport_enable(cf_classifier *cl) {
+    if (!cl) return CF_ERR_ARG;
+    return guard([&] {
+        if (cl->kreportOn) return;
+        const HostIndex &h = cl->ix->h;
+        cfamd::kreport::Taxonomy tx;
+        tx.quiet = true;
+        tx.load(h, false);
+        const std::vector<uint64_t> tab = cfamd::kreport::lcaTable(tx, h.taxa, kLcaOutside);      // (throws on a cycle)
+        HIP_OK(hipSetDevice(cl->ix->device));
+        cl->lcaTab.upload(tab);
+        cl->kreportCounts.alloc(h.taxa.size() + 1);
+        HIP_OK(hipMemset(cl->kreportCounts.p, 0, cl->kreportCounts.bytes()));
+        cl->kreportOn = true;
+    });
+}
+cf_status cf_kreport_reset(cf_classifier *cl) {
+    if (!cl) return CF_ERR_ARG;
+    if (!cl->kreportOn) { g_err = "cf_kreport_reset: cf_kreport_enable has not been called on this classifier"; return CF_ERR_ARG; }
+    return guard([&] { HIP_OK(hipSetDevice(cl->ix->device)); HIP_OK(hipMemset(cl->kreportCounts.p, 0, cl->kreportCounts.bytes())); });
+}
+cf_status cf_kreport_get(cf_classifier *cl, uint64_t *perTaxon, uint64_t *nReads) {
+    if (!cl || !perTaxon || !nReads) return CF_ERR_ARG;
+    if (!cl->kreportOn) { g_err = "cf_kreport_get: cf_kreport_enable has not been called on this classifier"; return CF_ERR_ARG; }
+    return guard([&] {
+        const size_t n = cl->ix->h.taxa.size();
+        HIP_OK(hipSetDevice(cl->ix->device));
+        HIP_OK(hipMemcpy(perTaxon, cl->kreportCounts.p, n * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(nReads, cl->kreportCounts.p + n, 8, hipMemcpyDeviceToHost));
+    });
+}
+cf_status cf_kreport_write(const cf_index *ix, const uint64_t *perTaxon, uint64_t nReads, const char *path) {
+    if (!ix || !perTaxon || !path) return CF_ERR_ARG;
+    return guard([&] {
+        cfamd::kreport::Taxonomy tx;
+        tx.load(ix->h, false);
+        cfamd::kreport::Report rp(tx);
+        for (size_t i = 0; i < ix->h.taxa.size(); i++) if (perTaxon[i]) rp.taxo[ix->h.taxa[i]] += (double)perTaxon[i];
+        rp.seqCount = (double)nReads;
+        std::FILE *f = std::fopen(path, "wb");
+        if (!f) throw ArgError(std::string("cannot open ") + path + " for writing: " + std::strerror(errno));
+        rp.to = f;
+        try { (void)rp.emit("centrifuge-kreport"); } catch (...) { std::fclose(f); throw; }      // (no reads: the script's message, an empty file)
+        if (std::fclose(f) != 0) throw std::runtime_error(std::string("error writing ") + path);
+    });
+}
+cf_status cf_batch_text_names(const cf_batch *bt, cf_text_names *out) {
+    if (!bt || !out) return CF_ERR_ARG;
+    if (!bt->namesValid || !bt->textDone) { g_err = "cf_batch_text_names: needs cf_kreport_enable on the classifier and a batch waited for with cf_batch_wait_text"; return CF_ERR_ARG; }
+    const TextNames &n = *bt->hTxNames.p;
+    *out = cf_text_names{};
+    out->n_dup = n.nDup; out->first_len = n.firstLen; out->last_len = n.lastLen; out->dup_len = n.dupLen;
+    std::memcpy(out->first, n.first, kTextNameBytes); std::memcpy(out->last, n.last, kTextNameBytes); std::memcpy(out->dup, n.dup, kTextNameBytes);
+    return CF_OK;
+}
+cf_status cf_batch_kreport_ms(const cf_batch *bt, float *ms) {
+    if (!bt || !ms) return CF_ERR_ARG;
+    *ms = bt->kreportMs;
+    return CF_OK;
 }
 cf_status cf_counts_get_single(cf_classifier *cl, uint64_t *nSingle) {
     if (!cl || !nSingle) return CF_ERR_ARG;

@@ -2921,6 +2921,88 @@ CF_DEV void count_body(const DBatch &b, uint32_t *lds, uint32_t chunk, uint32_t 
     }
 }
 
+// ------------------------------------------------------------------ the Kraken-style report's tally (cf_kreport_enable)
+// What `centrifuge-kreport` (cf_kreport.cpp, its default mode) makes of a read's rows: ONE taxon, the lowest common ancestor of the
+// rows' taxa, and a count per such taxon.  The rows are on the device behind the score stage, so the tally is a sibling of
+// count_body — no text is read for it.
+//
+// The tree as the host lays it out (cfamd::kreport::lcaTable, cf_kreport_tree.hpp), one 8-byte entry per dense taxon: parent's dense
+// index | depth << 32 (a root: its own index, depth 0) — a step up the tree is one load.  kLcaOutside in the depth marks a taxon
+// whose chain of parents leaves the tree: centrifuge-kreport counts its rows under taxon 1 (inTree, centrifuge-kreport:161-175).
+constexpr uint32_t kLcaOutside = 0x80000000u, kLcaMaxDepth = 4096;
+CF_DEV uint32_t lca_parent(uint64_t e) { return (uint32_t)e; }
+CF_DEV uint32_t lca_depth(uint64_t e) { return (uint32_t)(e >> 32); }
+// a row's taxon as the fold sees it: itself, or taxon 1 when it is outside the tree
+CF_DEV uint32_t lca_inside(const uint64_t *tab, uint32_t t) { return (lca_depth(tab[t]) & kLcaOutside) ? 1u : t; }
+// Taxonomy::lca (centrifuge-kreport:177-203) of two taxa INSIDE the tree (lca_inside): 0 is the fold's neutral element, the deeper
+// node climbs to the other's depth, then both climb until they meet; chains that end at different roots meet at taxon 1.  The depths
+// are counted down locally, so the loops end after kLcaMaxDepth steps whatever the table holds.
+CF_DEV uint32_t lca_body(const uint64_t *tab, uint32_t a, uint32_t b) {
+    if (a == 0) return b;
+    if (b == 0 || a == b) return a;
+    uint32_t da = lca_depth(tab[a]), db = lca_depth(tab[b]);
+    da = da > kLcaMaxDepth ? kLcaMaxDepth : da; db = db > kLcaMaxDepth ? kLcaMaxDepth : db;
+    for (; da > db; da--) a = lca_parent(tab[a]);
+    for (; db > da; db--) b = lca_parent(tab[b]);
+    for (; a != b && da > 0; da--) { a = lca_parent(tab[a]); b = lca_parent(tab[b]); }
+    return a == b ? a : 1u;
+}
+
+struct DKreport {
+    const uint64_t *lcaTab;      // nTaxa entries (above)
+    unsigned long long *counts;  // nTaxa + 1: reads per LCA taxon, then the total of reads
+    uint32_t k;                  // rows a query owns in DBatch::out (DParams::k)
+    uint32_t chunk;              // queries per block (kCountChunk; the harness lowers it)
+};
+// block `chunk` of the pass's window, count_body's way: a query folds the taxa of its printed rows (none: taxon 0, the
+// "unclassified" line) — from o1b when it prints up to kFieldRows rows, from its k slots in `out` when more —, the blocks add the
+// results up in LDS and send one 64-bit atomic per taxon seen, plus one for the reads.  lds = keys[nSlots], reads[nSlots], total[1].
+CF_DEV void kreport_body(const DBatch &b, const DKreport &kr, uint32_t *lds, uint32_t chunk, uint32_t slotBits, bool direct) {
+    const uint32_t t = cf_local_thread(), nt = cf_block_threads();
+    const uint32_t nSlots = 1u << slotBits;
+    uint32_t *keys = lds, *cnt = lds + nSlots, *total = lds + 2 * nSlots;
+    for (uint32_t i = t; i < nSlots; i += nt) { keys[i] = kCountEmpty; cnt[i] = 0; }
+    if (t == 0) *total = 0;
+    cf_block_sync();
+    const uint32_t q0 = chunk * kr.chunk, qLo = b.st->qLo, qHi = b.st->qHi;
+    uint32_t mine = 0;
+    for (uint32_t i = t; i < kr.chunk; i += nt) {
+        const uint32_t q = q0 + i;
+        if (q < q0 || q < qLo || q >= qHi) continue;
+        const uint32_t no = b.nOut[q] < kr.k ? b.nOut[q] : kr.k;
+        uint32_t acc = 0;
+        if (no <= kFieldRows) {
+#pragma unroll
+            for (uint32_t j = 0; j < kFieldRows; j++) {
+                if (j >= no) continue;
+                const uint32_t tidx = (uint32_t)(b.o1b[j * b.oStride + q] >> 32);
+                if (tidx < b.nTaxa) acc = lca_body(kr.lcaTab, acc, lca_inside(kr.lcaTab, tidx));     // (else: not on a well-formed index)
+            }
+        } else for (uint32_t j = 0; j < no; j++) {
+            const uint32_t tidx = b.out[(uint64_t)q * kr.k + j].tidx;
+            if (tidx < b.nTaxa) acc = lca_body(kr.lcaTab, acc, lca_inside(kr.lcaTab, tidx));
+        }
+        mine++;
+        const uint32_t h = direct ? acc : (acc * 0x9e3779b1u) >> (32u - slotBits);
+        bool placed = false;
+        for (uint32_t pr = 0; pr < kCountProbes && !placed; pr++) {
+            const uint32_t s = (h + pr) & (nSlots - 1);
+            uint32_t k = keys[s];
+            if (k == kCountEmpty) k = cf_atomic_cas(&keys[s], kCountEmpty, acc);
+            if (k == kCountEmpty || k == acc) { cf_atomic_add(&cnt[s], 1u); placed = true; }
+        }
+        if (!placed) cf_atomic_add(&kr.counts[acc], 1ull);
+    }
+    if (mine) cf_atomic_add(total, mine);
+    cf_block_sync();
+    for (uint32_t i = t; i < nSlots; i += nt) {
+        const uint32_t k = keys[i], n = cnt[i];
+        if (k == kCountEmpty || n == 0) continue;
+        cf_atomic_add(&kr.counts[k], (unsigned long long)n);
+    }
+    if (t == 0 && *total) cf_atomic_add(&kr.counts[b.nTaxa], (unsigned long long)*total);
+}
+
 // score_body for the common query, in registers: its planned hits are inline (qplan: at most kInlinePlan), it resolved at most
 // kScoreFastRows rows, they lead to at most kFastEntries hit-map entries, and those are no more than k (no climb:
 // classifier.h:399).  Everything the general kernel does for such a query — hit map with the ts rule (classifier.h:305-378,

@@ -19,13 +19,15 @@
 #include <unordered_set>
 #include <vector>
 
+#include <zlib.h>
+
 #include "cf_index.hpp"
+#include "cf_kreport_tree.hpp"
 
 using namespace cfamd;
+using namespace cfamd::kreport;
 
 namespace {
-
-constexpr uint64_t kJunk = ~0ull;          // a taxID field that is not a number (e.g. the header line of a second file)
 
 struct Opts {
     std::string index;
@@ -73,15 +75,66 @@ Opts parse(int argc, char **argv) {
     return o;
 }
 
-// concatenation of the input files ('-' or none = stdin) — Perl's <>
+// concatenation of the input files ('-' or none = stdin) — Perl's <>.  An input whose first bytes are the gzip magic is inflated as
+// it is read (what centrifuge-class --out-bgzf writes: BGZF is concatenated gzip members); anything else is taken as it is.
 struct Lines {
     std::vector<std::string> files;
     size_t next = 0;
     std::FILE *f = nullptr;
-    char *buf = nullptr;
-    size_t cap = 0;
-    explicit Lines(std::vector<std::string> fs) : files(std::move(fs)) { if (files.empty()) files.push_back("-"); }
-    ~Lines() { if (f && f != stdin) std::fclose(f); std::free(buf); }
+    std::vector<char> buf, zin;        // buf[lo, hi): text not handed out yet
+    size_t lo = 0, hi = 0;
+    bool eof = false, first = true, gz = false, zEnd = false;
+    z_stream z{};
+    explicit Lines(std::vector<std::string> fs) : files(std::move(fs)), buf(1u << 20), zin(1u << 18) { if (files.empty()) files.push_back("-"); }
+    ~Lines() { closeFile(); }
+    void closeFile() { if (gz) { inflateEnd(&z); gz = false; } if (f && f != stdin) std::fclose(f); f = nullptr; }
+    // more text behind buf[hi); false at the end of the file
+    bool fill() {
+        if (eof) return false;
+        if (lo > 0) { std::memmove(buf.data(), buf.data() + lo, hi - lo); hi -= lo; lo = 0; }
+        if (hi == buf.size()) buf.resize(buf.size() * 2);
+        if (first) {                                           // the file's first bytes decide
+            first = false;
+            const size_t n = std::fread(buf.data(), 1, 2, f);
+            if (n == 2 && (uint8_t)buf[0] == 0x1f && (uint8_t)buf[1] == 0x8b) {
+                z = z_stream{};
+                if (inflateInit2(&z, 15 + 16) != Z_OK) throw std::runtime_error("zlib: inflateInit2 failed");
+                gz = true; zEnd = false;
+                std::memcpy(zin.data(), buf.data(), 2);
+                z.next_in = reinterpret_cast<Bytef *>(zin.data()); z.avail_in = 2;
+            } else { hi = n; if (n < 2) eof = true; return n > 0; }
+        }
+        if (!gz) {
+            const size_t n = std::fread(buf.data() + hi, 1, buf.size() - hi, f);
+            if (n == 0) { eof = true; return false; }
+            hi += n;
+            return true;
+        }
+        for (;;) {
+            if (z.avail_in == 0) {
+                const size_t n = std::fread(zin.data(), 1, zin.size(), f);
+                if (n == 0) {                                  // (in the middle of a member: what was inflated so far has been handed out)
+                    if (!zEnd) std::fprintf(stderr, "centrifuge-kreport: the gzip input ends in the middle of a member: the report covers what came before\n");
+                    eof = true; return false;
+                }
+                z.next_in = reinterpret_cast<Bytef *>(zin.data()); z.avail_in = (uInt)n;
+            }
+            if (zEnd) {                                        // a further member?
+                if ((uint8_t)z.next_in[0] != 0x1f) {
+                    std::fprintf(stderr, "centrifuge-kreport: bytes that are no gzip member behind the last member of the input: ignored\n");
+                    eof = true; return false;
+                }
+                inflateReset(&z); zEnd = false;
+            }
+            const size_t room = std::min<size_t>(buf.size() - hi, 1u << 30);
+            z.next_out = reinterpret_cast<Bytef *>(buf.data() + hi); z.avail_out = (uInt)room;
+            const int rc = inflate(&z, Z_NO_FLUSH);
+            const size_t got = room - z.avail_out;
+            if (rc == Z_STREAM_END) zEnd = true;
+            else if (rc != Z_OK && rc != Z_BUF_ERROR) { std::fprintf(stderr, "centrifuge-kreport: corrupt gzip input\n"); eof = true; if (got) { hi += got; return true; } return false; }
+            if (got) { hi += got; return true; }
+        }
+    }
     // line without its '\n'; false at the end of the last file
     bool get(const char *&p, size_t &n) {
         for (;;) {
@@ -92,15 +145,20 @@ struct Lines {
                 else {
                     f = std::fopen(path.c_str(), "rb");
                     if (!f) { std::fprintf(stderr, "Can't open %s: %s.\n", path.c_str(), std::strerror(errno)); continue; }
-                    std::setvbuf(f, nullptr, _IOFBF, 1 << 20);
                 }
+                lo = hi = 0; eof = false; first = true;
             }
-            const ssize_t r = getline(&buf, &cap, f);
-            if (r < 0) { if (f != stdin) std::fclose(f); f = nullptr; continue; }
-            n = (size_t)r;
-            if (n && buf[n - 1] == '\n') n--;
-            p = buf;
-            return true;
+            size_t from = lo;
+            for (;;) {
+                if (const char *nl = static_cast<const char *>(std::memchr(buf.data() + from, '\n', hi - from))) {
+                    p = buf.data() + lo; n = (size_t)(nl - p); lo = (size_t)(nl - buf.data()) + 1;
+                    return true;
+                }
+                from = hi - lo;                                // (fill moves the text to the front)
+                if (!fill()) break;
+            }
+            if (hi > lo) { p = buf.data() + lo; n = hi - lo; lo = hi; return true; }      // a last line without '\n'
+            closeFile();
         }
     }
 };
@@ -111,99 +169,6 @@ bool parseId(const char *p, size_t n, uint64_t &v) {
     for (size_t i = 0; i < n; i++) { if (p[i] < '0' || p[i] > '9') return false; v = v * 10 + (uint64_t)(p[i] - '0'); }
     return true;
 }
-
-struct Taxonomy {
-    std::vector<uint64_t> tid, parent;          // ascending tid: the order `centrifuge-inspect --taxonomy-tree` lists them
-    std::vector<uint8_t> rank;
-    std::unordered_map<uint64_t, uint32_t> at;  // tid -> position
-    std::unordered_map<uint64_t, std::vector<uint64_t>> children;
-    std::unordered_map<uint64_t, std::string> names;
-    std::unordered_set<uint64_t> warned;
-
-    bool parentOf(uint64_t a, uint64_t &p) const { auto it = at.find(a); if (it == at.end()) return false; p = parent[it->second]; return true; }
-    void warnNoParent(uint64_t a) { std::fprintf(stderr, "Couldn't find parent of taxID %" PRIu64 " - directly assigned to root.\n", a); }
-
-    bool inTree(uint64_t a) {                                              // centrifuge-kreport:161-175
-        if (a == kJunk) return true;
-        while (a > 1) {
-            uint64_t p;
-            if (!parentOf(a, p)) { warnNoParent(a); return false; }
-            if (a == p) break;
-            a = p;
-        }
-        return true;
-    }
-    uint64_t lca(uint64_t a, uint64_t b) {                                 // centrifuge-kreport:177-203
-        if (a == 0) return b;
-        if (b == 0) return a;
-        if (a == b) return a;
-        std::unordered_set<uint64_t> path;
-        while (a != 0) {                                                   // Perl: `$a ge 1` on the decimal string
-            path.insert(a);
-            uint64_t p;
-            if (a == kJunk || !parentOf(a, p)) { warnNoParent(a); break; }
-            if (a == p) break;
-            a = p;
-        }
-        while (b > 1 && b != kJunk) {
-            if (path.count(b)) return b;
-            uint64_t p;
-            if (!parentOf(b, p)) { warnNoParent(b); break; }
-            if (b == p) break;
-            b = p;
-        }
-        return 1;
-    }
-};
-
-const char *rankCode(const char *r) {                                      // centrifuge-kreport:205-218
-    static const std::pair<const char *, const char *> k[] = {{"species", "S"}, {"genus", "G"}, {"family", "F"}, {"order", "O"},
-                                                              {"class", "C"}, {"phylum", "P"}, {"kingdom", "K"}, {"superkingdom", "D"}};
-    for (const auto &e : k) if (std::strcmp(r, e.first) == 0) return e.second;
-    return "-";
-}
-
-struct Report {
-    Taxonomy &tx;
-    std::unordered_map<uint64_t, double> taxo, clade;
-    double seqCount = 0;
-    bool showZeros = false;
-    std::string out;
-
-    double cladeOf(uint64_t t) const { auto it = clade.find(t); return it == clade.end() ? 0.0 : it->second; }
-    double taxoOf(uint64_t t) const { auto it = taxo.find(t); return it == taxo.end() ? 0.0 : it->second; }
-
-    void sum(uint64_t node, int depth) {                                   // dfs_summation, centrifuge-kreport:220-230
-        if (depth > 4096) throw std::runtime_error("taxonomy tree is deeper than 4096 levels (a cycle?)");
-        auto it = tx.children.find(node);
-        if (it == tx.children.end()) return;
-        for (uint64_t c : it->second) {
-            sum(c, depth + 1);
-            clade[node] += cladeOf(c);
-        }
-    }
-    void line(double cladeCnt, double taxoCnt, const char *code, uint64_t id, int depth, const std::string &name) {
-        char b[128];
-        std::snprintf(b, sizeof b, "%6.2f\t%lld\t%lld\t%s\t%" PRIu64 "\t", cladeCnt * 100 / seqCount, (long long)cladeCnt, (long long)taxoCnt, code, id);
-        out += b;
-        out.append((size_t)depth * 2, ' ');
-        out += name;
-        out.push_back('\n');
-        if (out.size() > (1u << 20)) { std::fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
-    }
-    void report(uint64_t node, int depth) {                                // dfs_report, centrifuge-kreport:138-159
-        const double c = cladeOf(node);
-        if (c == 0 && !showZeros) return;
-        auto at = tx.at.find(node);
-        auto nm = tx.names.find(node);
-        line(c, taxoOf(node), rankCode(at == tx.at.end() ? "" : rankString(tx.rank[at->second])), node, depth, nm == tx.names.end() ? std::string() : nm->second);
-        auto it = tx.children.find(node);
-        if (it == tx.children.end()) return;
-        std::vector<uint64_t> kids = it->second;
-        std::stable_sort(kids.begin(), kids.end(), [&](uint64_t a, uint64_t b) { return cladeOf(a) > cladeOf(b); });   // Perl's sort is a stable merge sort
-        for (uint64_t k : kids) report(k, depth + 1);
-    }
-};
 
 }  // namespace
 
@@ -219,19 +184,10 @@ int main(int argc, char **argv) {
             if (std::FILE *t = std::fopen((base + ".1.cf").c_str(), "rb")) std::fclose(t);
             else if (const char *e = std::getenv("CENTRIFUGE_INDEXES")) base = std::string(e) + "/" + o.index;
             h.load(base, nullptr);
-            std::fprintf(stderr, "Loading names file ...\n");
-            for (const auto &e : h.names) tx.names[e.first] = e.second;     // a repeated taxid keeps the last name
-            std::fprintf(stderr, "Loading nodes file ...\n");
-            for (const auto &nd : h.tree) {                                  // centrifuge-kreport:247-259
-                const uint64_t par = nd.tid == 1 ? 0 : nd.parent;
-                tx.at[nd.tid] = (uint32_t)tx.tid.size();
-                tx.tid.push_back(nd.tid); tx.parent.push_back(par); tx.rank.push_back(nd.rank);
-                tx.children[par].push_back(nd.tid);
-            }
+            tx.load(h, true);
         }
-        Report rp{tx};
+        Report rp(tx);
         rp.showZeros = o.showZeros;
-        rp.taxo[0] = 0;
         Lines in(o.files);
         const char *p; size_t n;
         if (o.countTable) {                                                  // centrifuge-kreport:74-79
@@ -289,13 +245,7 @@ int main(int argc, char **argv) {
                 prevRead.assign(rd.first, rd.second); havePrev = true;
             }
         }
-        rp.clade = rp.taxo;
-        rp.sum(1, 0);
-        if (!(rp.seqCount > 0)) { std::fprintf(stderr, "No sequence matches with given settings at %s line 133.\n", argv[0]); return 255; }
-        rp.line(rp.cladeOf(0), rp.taxoOf(0), "U", 0, 0, "unclassified");
-        rp.report(1, 0);
-        std::fwrite(rp.out.data(), 1, rp.out.size(), stdout);
-        std::fflush(stdout);
+        if (const int rc = rp.emit(argv[0])) return rc;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "centrifuge-kreport: %s\n", e.what());
         return 1;

@@ -79,7 +79,11 @@ struct u64x2 { uint64_t x, y; };
 inline u64x2 cf_load16(const uint8_t *p) { u64x2 v; std::memcpy(&v, p, 16); return v; }
 inline uint64_t cf_load8(const uint8_t *p) { uint64_t v; std::memcpy(&v, p, 8); return v; }
 inline void cf_wait_vmem() {}
+#ifdef CF_EMU_WAVE64
+inline void cf_block_sync() { if (emu_wave_lane() >= 0) (void)emu_collective(EMU_OP_FENCE, 0, 0); }   // a block of one wavefront's fibers: they all meet here
+#else
 inline void cf_block_sync() {}                       // a one-thread block
+#endif
 inline void cf_store16_stream(void *p, uint64_t a, uint64_t b) { uint64_t v[2] = {a, b}; std::memcpy(p, v, 16); }
 }  // namespace cfamd
 #else

@@ -56,7 +56,8 @@ struct TextStatus {
     unsigned long long nWords[kTextStripes], nBases[kTextStripes];   // sums over the records: packed words, bases
     unsigned long long outBytes;                        // egress: bytes of the formatted rows
     uint32_t maxLen, flags;
-    uint32_t tupleWords, pad;                           // egress: words of the tuple list that are filled
+    uint32_t tupleWords, dupNames;                      // egress: words of the tuple list that are filled; queries whose readID equals their predecessor's
+                                                        // (text_dup_body, with the Kraken-style tally on: no bit of `flags` — the block is still the device's)
     unsigned long long words() const { unsigned long long t = 0; for (uint32_t i = 0; i < kTextStripes; i++) t += nWords[i]; return t; }
     unsigned long long bases() const { unsigned long long t = 0; for (uint32_t i = 0; i < kTextStripes; i++) t += nBases[i]; return t; }
 };
@@ -469,6 +470,48 @@ CF_DEV void text_record_body_t(const DTextRec &d, uint32_t r) {
         if (mx > d.st->maxLen) cf_atomic_max(&d.st->maxLen, mx);      // (the plain read only spares atomics that would change nothing)
         if (flags) cf_atomic_or(&d.st->flags, flags);
     }
+}
+
+// ---- with the Kraken-style tally on (cf_kreport_enable): centrifuge-kreport merges NEIGHBOURING rows of equal readID, so two
+// neighbouring reads of one name are one read to it and two to the tally.  One thread per query compares its readID with its
+// predecessor's and counts the equal ones (TextStatus::dupNames); the batch's first and last readID (their lengths, up to 255 bytes
+// of each) and the first such pair's go back to the host, which compares neighbouring batches (cf_batch_text_names).
+constexpr uint32_t kTextNameBytes = 255;
+struct TextNames {
+    uint32_t nDup, dupKey;                              // dupKey = ~(the lowest query that repeats its predecessor's readID); 0: none
+    uint32_t firstLen, lastLen, dupLen, pad;
+    uint8_t first[kTextNameBytes + 1], last[kTextNameBytes + 1], dup[kTextNameBytes + 1];
+};
+struct DTextDup {
+    const uint8_t *text;
+    const uint32_t *idOff, *idLen;
+    uint32_t nQueries, paired;                          // (mates: the row carries mate 1's readID)
+    TextStatus *st;
+    TextNames *names;
+};
+CF_DEV void text_name_copy(const DTextDup &d, uint32_t q, uint8_t *to, uint32_t &len) {
+    const uint32_t r = d.paired ? 2 * q : q, n = d.idLen[r];
+    const uint8_t *p = d.text + d.idOff[r];
+    for (uint32_t i = 0; i < n && i < kTextNameBytes; i++) to[i] = p[i];
+    len = n;
+}
+CF_DEV void text_dup_body(const DTextDup &d, uint32_t q) {
+    if (q >= d.nQueries) return;
+    if (q == 0) text_name_copy(d, q, d.names->first, d.names->firstLen);
+    if (q == d.nQueries - 1) text_name_copy(d, q, d.names->last, d.names->lastLen);
+    if (q == 0) return;
+    const uint32_t r = d.paired ? 2 * q : q, rp = d.paired ? 2 * (q - 1) : q - 1, n = d.idLen[r];
+    if (d.idLen[rp] != n) return;
+    const uint8_t *a = d.text + d.idOff[r], *b = d.text + d.idOff[rp];
+    for (uint32_t i = 0; i < n; i++) if (a[i] != b[i]) return;
+    cf_atomic_add(&d.st->dupNames, 1u);
+    cf_atomic_add(&d.names->nDup, 1u);
+    cf_atomic_max(&d.names->dupKey, ~q);
+}
+// ... behind it, one thread: the readID of the first pair found
+CF_DEV void text_dup_name_body(const DTextDup &d) {
+    if (d.names->dupKey == 0) return;
+    text_name_copy(d, ~d.names->dupKey, d.names->dup, d.names->dupLen);
 }
 
 CF_DEV void text_record_body(const DTextRec &d, uint32_t r) {

@@ -553,6 +553,39 @@ cf_status cf_counts_get(cf_classifier *, uint64_t *n_reads, uint64_t *n_unique);
  * of the batches whose rows were formatted on the device (cf_batch_wait_text), summed by the all-reduce along with the others */
 cf_status cf_counts_get_single(cf_classifier *, uint64_t *n_single);
 void     *cf_counts_device(cf_classifier *);
+/* ------------------------------------------------------------- Kraken-style report
+ * What `centrifuge-kreport -x <index> <classification output>` prints (its default mode: one count per read at the lowest common
+ * ancestor of the taxa on the read's rows, no filters), tallied on the device behind the score stage instead of from the text.
+ * cf_kreport_enable lays the tree out for the device (a parent | depth entry per dense taxon; CF_ERR_* with the tool's
+ * message when the tree is deeper than 4,096 levels, i.e. has a cycle) and allocates num_taxa + 1 u64 counters of its own — apart
+ * from cf_counts_device and its all-reduce.  From then on every cf_classify / cf_batch_submit* of the classifier adds one launch
+ * that folds each query's printed rows (any number of them, up to the classifier's k) and counts the result; a query that prints
+ * no row counts under taxon 0.  Without the call nothing is launched or allocated.  cf_kreport_get reads the counters back
+ * (per_taxon: num_taxa entries, dense order; n_reads: the queries counted) once the caller has waited for its batches — the call
+ * itself does not synchronise with the slots' streams: a batch still in flight is counted in part or not at all; the
+ * counters of several classifiers (GPUs, processes) are added by the caller.  cf_kreport_write makes the tree sums and prints
+ * the report to `path` with the code centrifuge-kreport itself prints with (a host index is enough); with n_reads == 0 the file
+ * is empty and the tool's "No sequence matches" message goes to stderr.
+ * The tool merges NEIGHBOURING rows with equal readIDs, so it counts two neighbouring reads of the same name as one; the tally
+ * is per read.  A caller that promises the tool's bytes has to find such pairs: among reads it parsed itself by comparing the
+ * names, in batches parsed on the device with cf_batch_text_names — while the tally is on, cf_batch_wait_text(_bgzf) also
+ * compares every query's readID with its predecessor's on the device and brings back the number of equal pairs, the readID of the
+ * first of them, and the batch's first and last readID (length, and up to 255 bytes of each: neighbouring batches are the caller's
+ * to compare; longer names that agree in length and in those bytes have to count as equal).  centrifuge-class --kreport-file
+ * refuses such input. */
+cf_status cf_kreport_enable(cf_classifier *);
+cf_status cf_kreport_reset(cf_classifier *);
+cf_status cf_kreport_get(cf_classifier *, uint64_t *per_taxon, uint64_t *n_reads);
+cf_status cf_kreport_write(const cf_index *, const uint64_t *per_taxon, uint64_t n_reads, const char *path);
+typedef struct {
+    uint64_t n_dup;                        /* queries whose readID equals that of the query before them */
+    uint32_t first_len, last_len, dup_len; /* whole lengths; the arrays hold min(length, 255) bytes */
+    uint32_t reserved_;
+    char     first[256], last[256], dup[256];
+} cf_text_names;
+cf_status cf_batch_text_names(const cf_batch *, cf_text_names *out);
+/* k_kreport's time in the first pass of the slot's last batch, from HIP events (0 when the tally is off) */
+cf_status cf_batch_kreport_ms(const cf_batch *, float *ms);
 /* The path's only collective: in-place sum of the counters over the ranks of
  * an RCCL communicator — ncclAllReduce(counts, counts, 3*num_taxa, ncclUint64, ncclSum, comm,
  * stream), enqueued on `stream` (hipStream_t or NULL).  `nccl_comm` is an ncclComm_t the caller

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """End-to-end wall time of the centrifuge-class front ends (ours vs the reference binary) on one
 FASTA file: index built by the GPU builder, reads sampled from the genomes.
-usage: cli_e2e.py <genomes> <genome length> <reads> [noref | outbgzf [other centrifuge-class]]   (outbgzf: our plain output against
---out-bgzf, another build's plain run beside them, and gzip -1 of the TSV on 16 cores)"""
+usage: cli_e2e.py <genomes> <genome length> <reads> [noref | outbgzf [other centrifuge-class] | kreport [other centrifuge-class]]
+(outbgzf: our plain output against --out-bgzf, another build's plain run beside them, and gzip -1 of the TSV on 16 cores;
+kreport: our plain run against --kreport-file, another build's plain run beside them, then centrifuge-kreport on the TSV)"""
 import os
 import subprocess
 import sys
@@ -65,6 +66,34 @@ def main():
             size = sum(os.path.getsize(os.path.join(parts, f)) for f in os.listdir(parts))
             print("gzip -1 of the plain TSV in 16 pieces at once: split %.2fs + gzip %.2fs, %d bytes (%.1f per read) ok=%s" % (t1 - t0, time.time() - t1, size, size / n, ok), flush=True)
             shutil.rmtree(parts, ignore_errors=True)
+        return
+    if len(sys.argv) > 4 and sys.argv[4] == "kreport":
+        # the run without and with --kreport-file (the Kraken-style tally on the device), three runs of each in turn — with a fifth
+        # argument another build's binary (the parent commit's) beside them: whole process, the -t lines (search phase, k_kreport's
+        # HIP-event time) —, then the second pass the flag replaces: centrifuge-kreport on the TSV the same run wrote
+        keep = ("ime", "search", "Device text", "Kraken")
+        kr = os.path.join(d, "kreport.txt")
+        forms = [("plain", ours, []), ("kreport", ours, ["--kreport-file", kr])] + ([("parent", sys.argv[5], [])] if len(sys.argv) > 5 else [])
+        for tag, exe, extra in forms * 3:
+            out = os.path.join(d, tag + ".out")
+            t0 = time.time()
+            r = subprocess.run([exe, "-f", "-t", "-p", "8", "-x", os.path.join(d, "idx"), "-U", os.path.join(d, "reads.fa"), "-S", out,
+                                "--report-file", os.path.join(d, tag + ".rep")] + extra, capture_output=True, text=True, timeout=300)
+            dt = time.time() - t0
+            print("%-9s wall %.2fs -> %.3g reads/s  rc=%d  output %d bytes | %s" % (tag, dt, n / dt, r.returncode, os.path.getsize(out),
+                  " ; ".join(l for l in r.stderr.splitlines() if any(k in l for k in keep))), flush=True)
+            if r.returncode != 0:
+                print(r.stderr[-2000:], flush=True)
+                sys.exit(1)
+        tool = os.path.join(ROOT, "centrifuge_amd", "bin", "centrifuge-kreport")
+        for i in range(2):
+            t0 = time.time()
+            with open(os.path.join(d, "tool.txt"), "wb") as f:
+                rc = subprocess.run([tool, "-x", os.path.join(d, "idx"), os.path.join(d, "kreport.out")], stdout=f, stderr=subprocess.DEVNULL, timeout=900).returncode
+            print("centrifuge-kreport on the TSV (%d bytes): wall %.2fs rc=%d" % (os.path.getsize(os.path.join(d, "kreport.out")), time.time() - t0, rc), flush=True)
+        same = open(os.path.join(d, "tool.txt"), "rb").read() == open(kr, "rb").read()
+        print("--kreport-file identical to centrifuge-kreport's output: %s (%d bytes); TSV identical to the plain run's: %s" % (
+            same, os.path.getsize(kr), subprocess.run(["cmp", "-s", os.path.join(d, "plain.out"), os.path.join(d, "kreport.out")]).returncode == 0), flush=True)
         return
     noref = len(sys.argv) > 4 and sys.argv[4] == "noref"
     runs = [("ours -p 8", ours, 8), ("ours -p 1", ours, 1)] + ([] if noref else [("reference -p 8", ref, 8)])
