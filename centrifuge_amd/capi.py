@@ -40,6 +40,29 @@ class OpCounts(C.Structure):
             16 * self.n_ftab + 8 * (self.n_ftab_wide + 2 * self.n_verify - self.n_pos_hits) + 32 * self.n_text_loads + sa_bytes * self.n_rows + per_read * n_reads
 
 
+SEARCH_FORMS = ("none", "words", "sides", "planes", "planes-lazy1", "planes-lazy2", "multi")     # CF_SEARCH_* of include/centrifuge_amd.h
+
+
+class LaunchRecord(C.Structure):
+    """cf_launch_record of include/centrifuge_amd.h: which kernels the slot's last batch was launched with"""
+    _fields_ = [("search_form", C.c_int32), ("rec_words", C.c_uint32), ("search_blocks", C.c_uint32), ("walk_version", C.c_int32),
+                ("post_fast", C.c_int32), ("post_cap_hits", C.c_uint32), ("score_fast", C.c_int32), ("score_cap_rows", C.c_uint32),
+                ("score_sparse", C.c_uint32), ("count_slot_bits", C.c_uint32), ("count_direct", C.c_int32),
+                ("direct_refs", C.c_int32), ("self_records", C.c_int32), ("rev_words", C.c_int32), ("lazy_hits", C.c_int32),
+                ("early_score", C.c_int32), ("tail_stream", C.c_int32), ("passes", C.c_uint32), ("pos_form", C.c_int32), ("pos_shift", C.c_uint32)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_}
+        d["search_form"] = SEARCH_FORMS[d["search_form"]]
+        return d
+
+
+def _launch_record(L, h):
+    r = LaunchRecord()
+    _check(L.cf_batch_debug_launch(h, C.byref(r)))
+    return r.as_dict()
+
+
 class PackedReads(C.Structure):
     """cf_packed_reads of include/centrifuge_amd.h"""
     _fields_ = [("bases", C.c_void_p), ("nmask", C.c_void_p), ("len", C.c_void_p), ("seeds", C.c_void_p),
@@ -151,7 +174,7 @@ EXPORTS = [
     "cf_index_uid", "cf_index_ref_taxid", "cf_index_taxon_id", "cf_format_seqid", "cf_tax_rank",
     "cf_tax_rank_string", "cf_tax_name", "cf_tax_size", "cf_params_default", "cf_classifier_create",
     "cf_classifier_destroy", "cf_batch_create", "cf_batch_destroy", "cf_batch_num_queries", "cf_gen_rand_seed",
-    "cf_classify", "cf_batch_results", "cf_batch_timings", "cf_batch_opcounts", "cf_counts_reset", "cf_counts_get",
+    "cf_classify", "cf_batch_results", "cf_batch_timings", "cf_batch_opcounts", "cf_batch_debug_launch", "cf_counts_reset", "cf_counts_get",
     "cf_counts_device", "cf_counts_allreduce", "cf_debug_search", "cf_debug_resolve", "cf_debug_rank", "cf_debug_rank1",
     "cf_debug_random_read_gbps", "cf_index_restore", "cf_batch_num_rows", "cf_batch_results_compact", "cf_batch_plan", "cf_batch_plan_ms",
     "cf_batch_max_scores", "cf_report_create", "cf_report_destroy", "cf_report_add", "cf_report_add_narrow", "cf_report_add_counts", "cf_report_reset_counts", "cf_report_write", "cf_report_serialize", "cf_report_merge",
@@ -213,7 +236,7 @@ def lib():
         "cf_batch_plan": (i32, [vp, vp]), "cf_batch_plan_ms": (i32, [vp, C.POINTER(C.c_float)]),
         "cf_batch_num_rows": (i32, [vp, C.POINTER(u64)]), "cf_batch_results_compact": (i32, [vp, vp, u64, vp, vp]),
         "cf_batch_timings": (i32, [vp, C.POINTER(C.c_float * 5)]),
-        "cf_batch_opcounts": (i32, [vp, C.POINTER(OpCounts)]),
+        "cf_batch_opcounts": (i32, [vp, C.POINTER(OpCounts)]), "cf_batch_debug_launch": (i32, [vp, C.POINTER(LaunchRecord)]),
         "cf_counts_reset": (i32, [vp]), "cf_counts_get": (i32, [vp, vp, vp]), "cf_counts_device": (vp, [vp]), "cf_counts_allreduce": (i32, [vp, vp, vp]),
         "cf_debug_search": (i32, [vp, vp, u64, vp, vp, u32, vp]),
         "cf_debug_resolve": (i32, [vp, vp, u64, vp]),
@@ -514,6 +537,12 @@ class Batch:
         np.cumsum(n_rows, out=first[1:])
         return rows, first, n_rows, score2
 
+    def info(self):
+        """planned rows, passes of the row stage and the queries the general kernels took, of the classified batch (cf_batch_wait)"""
+        r = Results()
+        _check(self.L.cf_batch_wait(self.h, C.byref(r)))
+        return {"planned_sa_rows": r.planned_sa_rows, "row_passes": r.row_passes, "slow_post": r.slow_post, "slow_score": r.slow_score}
+
     def timings(self):
         ms = (C.c_float * 5)()
         _check(self.L.cf_batch_timings(self.h, C.byref(ms)))
@@ -528,6 +557,10 @@ class Batch:
         o = OpCounts()
         _check(self.L.cf_batch_opcounts(self.h, C.byref(o)))
         return o
+
+    def launch_record(self):
+        """which kernels the last batch was launched with (cf_batch_debug_launch) -> dict"""
+        return _launch_record(self.L, self.h)
 
 
 def pack_reads(seq, off):
@@ -823,6 +856,10 @@ class Slot:
         o = OpCounts()
         _check(self.L.cf_batch_opcounts(self.h, C.byref(o)))
         return o
+
+    def launch_record(self):
+        """which kernels the last batch was launched with (cf_batch_debug_launch) -> dict"""
+        return _launch_record(self.L, self.h)
 
     def close(self):
         if self.h:

@@ -551,6 +551,7 @@ struct cf_batch {
     double rowsPerQuery = 0;                 // printed rows per query of the slot's last batch (0 = none yet): sizes the next download
     double plannedPerQuery = 0;              // planned SA rows per query of the slot's last batch: sizes the row workspace
     uint32_t passes = 0;                     // passes of the row stage the last batch took
+    cf_launch_record rec{};                  // which kernels the last batch was launched with (cf_batch_debug_launch)
     float planMs = 0;
     float ms[5] = {0, 0, 0, 0, 0};
     OpCounts lastOps{};
@@ -982,7 +983,7 @@ void makePosTables(cf_index &ix) {
             seq[sq].y = j < nFrag ? frag[j].x : n;
         }
     }
-    const uint32_t sh = 14;
+    const uint32_t sh = (uint32_t)std::clamp(envInt("CF_POS_SHIFT", 14), 3, 14);      // (tests: small buckets = several fragments per bucket, buckets without a fragment start)
     const uint64_t nB = (n >> sh) + 2;
     std::vector<uint32_t> bucket(nB + 1);
     uint64_t f = 0;
@@ -1137,6 +1138,7 @@ bool launchSearch(cf_classifier *cl, cf_batch *bt, hipStream_t st, int blocksCap
     if (blocksCap) blocks = std::min(blocks, blocksCap);
     const DBatch &d = bt->d;
     const dim3 gr(blocks), bl(256);
+    auto note = [&](int form, const dim3 &g) { if (!count) { bt->rec.search_form = form; bt->rec.rec_words = bt->recWords; bt->rec.search_blocks = g.x; } };
     if (v2 && ix.d.planes) {
         int per = ix.occPlanes[wi] > 0 ? ix.occPlanes[wi] : 4;
         if (cfamd::cf_knob("CF_BLOCKS_PER_CU")) per = std::min(per, blocksPerCU());
@@ -1150,30 +1152,33 @@ bool launchSearch(cf_classifier *cl, cf_batch *bt, hipStream_t st, int blocksCap
         auto gridOf = [&](int pc) { const int n = persistentBlocks(ix, 2 * bt->nReads, pc > 0 ? pc : per, 1); return dim3(blocksCap ? std::min(blocksCap, n) : n); };
         if (ix.d.multiRows) {      // small ranges against the text (small_range_rows): kernels of their own — the states cost registers
             const dim3 gm = gridOf(ix.occMulti[wi]);
+            note(CF_SEARCH_MULTI, gm);
             if (bt->recWords == 4) { if (count) hipLaunchKernelGGL((k_search2_l1<4, true, 0, true>), gm, bl, 0, st, ix.d, cl->d, d); else hipLaunchKernelGGL((k_search2_l1<4, false, 0, true>), gm, bl, 0, st, ix.d, cl->d, d); }
             else if (bt->recWords == 6) { if (count) hipLaunchKernelGGL((k_search2_l1<6, true, 0, true>), gm, bl, 0, st, ix.d, cl->d, d); else hipLaunchKernelGGL((k_search2_l1<6, false, 0, true>), gm, bl, 0, st, ix.d, cl->d, d); }
             else { if (count) hipLaunchKernelGGL((k_search2_l1<8, true, 0, true>), gm, bl, 0, st, ix.d, cl->d, d); else hipLaunchKernelGGL((k_search2_l1<8, false, 0, true>), gm, bl, 0, st, ix.d, cl->d, d); }
         } else if (bt->recWords == 4) {
             if (count) hipLaunchKernelGGL((k_search2_l1<4, true>), g1, bl, 0, st, ix.d, cl->d, d);
-            else if (lazyN == 1) hipLaunchKernelGGL((k_search2_l1<4, false, 1>), gridOf(ix.occLazy[0]), bl, 0, st, ix.d, cl->d, d);   // one lazy hit, 22.5 KB of LDS, 72 VGPRs: seven blocks per CU instead of six
-            else hipLaunchKernelGGL((k_search2_l1<4, false>), g1, bl, 0, st, ix.d, cl->d, d);
+            else if (lazyN == 1) { note(CF_SEARCH_PLANES_LAZY1, gridOf(ix.occLazy[0])); hipLaunchKernelGGL((k_search2_l1<4, false, 1>), gridOf(ix.occLazy[0]), bl, 0, st, ix.d, cl->d, d); }   // one lazy hit, 22.5 KB of LDS, 72 VGPRs: seven blocks per CU instead of six
+            else { note(CF_SEARCH_PLANES, g1); hipLaunchKernelGGL((k_search2_l1<4, false>), g1, bl, 0, st, ix.d, cl->d, d); }
         } else if (bt->recWords == 6) {
             if (count) hipLaunchKernelGGL((k_search2_l1<6, true>), g1, bl, 0, st, ix.d, cl->d, d);
-            else if (lazyN == 2) hipLaunchKernelGGL((k_search2_l1<6, false, 2>), gridOf(ix.occLazy[1]), bl, 0, st, ix.d, cl->d, d);
-            else hipLaunchKernelGGL((k_search2_l1<6, false>), g1, bl, 0, st, ix.d, cl->d, d);
+            else if (lazyN == 2) { note(CF_SEARCH_PLANES_LAZY2, gridOf(ix.occLazy[1])); hipLaunchKernelGGL((k_search2_l1<6, false, 2>), gridOf(ix.occLazy[1]), bl, 0, st, ix.d, cl->d, d); }
+            else { note(CF_SEARCH_PLANES, g1); hipLaunchKernelGGL((k_search2_l1<6, false>), g1, bl, 0, st, ix.d, cl->d, d); }
         } else {
             if (count) hipLaunchKernelGGL((k_search2_l1<8, true>), g1, bl, 0, st, ix.d, cl->d, d);
-            else if (lazyN == 2) hipLaunchKernelGGL((k_search2_l1<8, false, 2>), gridOf(ix.occLazy[2]), bl, 0, st, ix.d, cl->d, d);
-            else hipLaunchKernelGGL((k_search2_l1<8, false>), g1, bl, 0, st, ix.d, cl->d, d);
+            else if (lazyN == 2) { note(CF_SEARCH_PLANES_LAZY2, gridOf(ix.occLazy[2])); hipLaunchKernelGGL((k_search2_l1<8, false, 2>), gridOf(ix.occLazy[2]), bl, 0, st, ix.d, cl->d, d); }
+            else { note(CF_SEARCH_PLANES, g1); hipLaunchKernelGGL((k_search2_l1<8, false>), g1, bl, 0, st, ix.d, cl->d, d); }
         }
         return count;
     }
     if (v2) {
+        note(CF_SEARCH_SIDES, gr);
         if (bt->recWords == 4) { if (count) hipLaunchKernelGGL((k_search2<2, 4, true>), gr, bl, 0, st, ix.d, cl->d, d); else hipLaunchKernelGGL((k_search2<2, 4, false>), gr, bl, 0, st, ix.d, cl->d, d); }
         else if (bt->recWords == 6) { if (count) hipLaunchKernelGGL((k_search2<2, 6, true>), gr, bl, 0, st, ix.d, cl->d, d); else hipLaunchKernelGGL((k_search2<2, 6, false>), gr, bl, 0, st, ix.d, cl->d, d); }
         else { if (count) hipLaunchKernelGGL((k_search2<2, 8, true>), gr, bl, 0, st, ix.d, cl->d, d); else hipLaunchKernelGGL((k_search2<2, 8, false>), gr, bl, 0, st, ix.d, cl->d, d); }
         return count;
     }
+    note(CF_SEARCH_WORDS, gr);
     hipLaunchKernelGGL(k_search<2>, gr, bl, 0, st, ix.d, cl->d, d);
     return true;
 }
@@ -1185,6 +1190,7 @@ bool launchWalk(cf_classifier *cl, cf_batch *bt, hipStream_t st, bool count = fa
     static const int wv = envInt("CF_WALK_V", 3);
     const uint64_t guess = std::min<uint64_t>(bt->d.rowsCap, std::max<uint64_t>(4 * bt->nQueries, 1024));
     const DBatch &d = bt->d;
+    if (!count) bt->rec.walk_version = wv == 2 ? 2 : 3;
     if (wv == 2) {
         const dim3 gr(persistentBlocks(ix, guess, blocksPerCU(), 2)), bl(256);
         if (count) hipLaunchKernelGGL((k_walk2<2, true>), gr, bl, 0, st, ix.d, d); else hipLaunchKernelGGL((k_walk2<2, false>), gr, bl, 0, st, ix.d, d);
@@ -1715,7 +1721,9 @@ static void enqueuePost(cf_batch *bt, hipStream_t st) {
     static const bool fast = envInt("CF_POST_FAST", 1) != 0;
     if (fast) hipLaunchKernelGGL(k_post_fast, dim3((nq + 255) / 256), dim3(256), 0, st, ix.d, cl->d, d);
     else hipLaunchKernelGGL(k_list_all, dim3((nq + 255) / 256), dim3(256), 0, st, bt->slowPost.p, &bt->st.p->nSlowPost, nq);
+    bt->rec.post_fast = fast ? 1 : 0; bt->rec.post_cap_hits = 0; bt->rec.early_score = 0;
     if (earlyScoreMode(bt)) {
+        bt->rec.early_score = 1;
         HIP_OK(hipEventRecord(bt->evPostFast, st));
         HIP_OK(hipStreamWaitEvent(bt->tail, bt->evPostFast, 0));
         hipLaunchKernelGGL(k_post, listGrid(ix, nq), dim3(64), 0, bt->tail, ix.d, cl->d, d, 0u);
@@ -1732,6 +1740,7 @@ static void enqueuePost(cf_batch *bt, hipStream_t st) {
     // 1.40 -> 1.56, config 5 (250-base reads: 54 KB per wavefront, two of them per CU) 1.85 -> 3.65.
     static const bool postLds = envInt("CF_POST_LDS", 0) != 0;
     const uint32_t capHits = postLds ? (uint32_t)std::min<uint64_t>(60, 2 * ((uint64_t)bt->maxLenHost / (uint64_t)std::max(1, ix.h.g.ftabChars) + 2)) : 0u;
+    bt->rec.post_cap_hits = capHits;
     hipLaunchKernelGGL(k_post, listGrid(ix, nq), dim3(64), (size_t)64 * capHits * sizeof(HitP), st, ix.d, cl->d, d, capHits);
 }
 
@@ -1748,13 +1757,17 @@ static bool enqueueRowPass(cf_batch *bt, uint32_t qLo, hipStream_t st, bool mark
     const bool direct = d.directRefs != 0;                  // (then the stage marks of "post" and "walk" end here: nothing is emitted or walked)
     if (nq && !direct) hipLaunchKernelGGL(k_emit, dim3((nq + 255) / 256), dim3(256), 0, st, cl->d, d);
     if (marks) HIP_OK(hipEventRecord(bt->ev[2], st));
+    if (direct) bt->rec.walk_version = 0;
+    bt->rec.direct_refs = direct ? 1 : 0;
     const bool counted = nq && !direct ? launchWalk(cl, bt, st) : true;
     if (marks) HIP_OK(hipEventRecord(bt->ev[3], st));
     if (nq) {
         if (early) {}                                       // (k_score_fast<true> ran behind k_post_fast)
         else if (fast) hipLaunchKernelGGL(k_score_fast<false>, dim3((nq + 255) / 256), dim3(256), 0, st, ix.d, cl->d, d);
         else hipLaunchKernelGGL(k_list_all, dim3((nq + 255) / 256), dim3(256), 0, st, bt->slowScore.p, &bt->st.p->nSlowScore, nq);   // (score_body skips what lies outside the window)
+        bt->rec.score_fast = early || fast ? 1 : 0;
         if (late && late != st) {                // the rest of the batch on the slot's own stream (CF_TAIL_STREAM=2, see enqueueClassify)
+            bt->rec.tail_stream = 2;
             HIP_OK(hipEventRecord(bt->evLate, st));
             HIP_OK(hipStreamWaitEvent(late, bt->evLate, 0));
             st = late;
@@ -1770,6 +1783,8 @@ static bool enqueueRowPass(cf_batch *bt, uint32_t qLo, hipStream_t st, bool mark
         // the others in place: score 2.45 -> 2.76 / 2.87 ms on the repeat-rich preset with the line drawn at 12 / 24 rows, profiles/r06k_*)
         hipLaunchKernelGGL(k_score, listGrid(ix, nq), dim3(64), (size_t)(64 / sparse) * score_scratch_bytes(capRows), st, ix.d, cl->d, d, capRows, capRows ? sparse : 1u, 0u, 0xffffffffu);
         static const uint32_t slotBits = (uint32_t)std::clamp(envInt("CF_COUNT_SLOT_BITS", (int)kCountSlotBits), 1, (int)kCountSlotBits);   // (tests: few slots = probing, overflow)
+        bt->rec.score_cap_rows = capRows; bt->rec.score_sparse = capRows ? sparse : 1u;
+        bt->rec.count_slot_bits = slotBits; bt->rec.count_direct = d.nTaxa <= (1u << slotBits) ? 1 : 0;
         hipLaunchKernelGGL(k_count, dim3((nq + kCountChunk - 1) / kCountChunk), dim3(1024), 0, st, d, slotBits, d.nTaxa <= (1u << slotBits));
         if (cl->kreportOn) {
             const bool timed = marks && bt->evKr[0];
@@ -1799,6 +1814,9 @@ static void enqueueCompact(cf_batch *bt, hipStream_t st) {
 static void enqueueClassify(cf_batch *bt, hipStream_t st) {
     cf_classifier *cl = bt->cl;
     bt->krTimed = false;
+    bt->rec = cf_launch_record{};
+    bt->rec.self_records = bt->selfRecords ? 1 : 0; bt->rec.rev_words = bt->revDelta != 0 ? 1 : 0; bt->rec.lazy_hits = (int32_t)(bt->d.lazyHits & 1u);
+    bt->rec.pos_form = cl->ix->d.posFrag ? 1 : 0; bt->rec.pos_shift = cl->ix->d.posShift;
     HIP_OK(hipMemsetAsync(bt->cursor.p, 0, 32, st));
     HIP_OK(hipMemsetAsync(bt->ops.p, 0, sizeof(OpCounts), st));
     // (qRows: every query's entry is written by one of the post kernels; nOut: by one of the score kernels — queries outside
@@ -1822,7 +1840,7 @@ static void enqueueClassify(cf_batch *bt, hipStream_t st) {
     static const int tailMode = envInt("CF_TAIL_STREAM", 0);
     hipStream_t ts = bt->tail && tailMode == 1 ? bt->tail : st;
     hipStream_t late = bt->tail && tailMode == 2 ? bt->tail : ts;
-    if (ts != st) HIP_OK(hipStreamWaitEvent(ts, bt->ev[1], 0));
+    if (ts != st) { HIP_OK(hipStreamWaitEvent(ts, bt->ev[1], 0)); bt->rec.tail_stream = 1; }
     const bool early = earlyScoreMode(bt);
     enqueuePost(bt, ts);
     scan_enqueue<SCAN_PLAIN>(bt->qRows.p, bt->nQueries, bt->qBase.p, nullptr, bt->tileA.p, bt->tileC.p, ts);
@@ -2977,6 +2995,13 @@ cf_status cf_batch_results_compact(cf_batch *bt, cf_row *rows, uint64_t rowsCap,
 cf_status cf_batch_timings(const cf_batch *bt, float ms[5]) {
     if (!bt || !ms) return CF_ERR_ARG;
     std::memcpy(ms, bt->ms, sizeof bt->ms);
+    return CF_OK;
+}
+cf_status cf_batch_debug_launch(const cf_batch *bt, cf_launch_record *out) {
+    if (!bt || !out) return CF_ERR_ARG;
+    if (!bt->finished) { g_err = "the batch has not been classified"; return CF_ERR_ARG; }
+    *out = bt->rec;
+    out->passes = bt->passes;
     return CF_OK;
 }
 cf_status cf_batch_opcounts(cf_batch *bt, cf_opcounts *o) {

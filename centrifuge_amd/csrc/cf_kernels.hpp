@@ -2638,6 +2638,7 @@ CF_DEV bool try_offset(const DIndex &ix, uint64_t row, uint32_t &ref) {
 // this very kernel, in its table-building modes, walks from every 2^walkRate-th row with the file's sample and stores
 // where it ends; the batch walks then stop at the first row of that denser table — on average 2^walkRate - 1 steps
 // instead of 2^offRate - 1 (15) — and read the same reference index the full walk would have reached.
+CF_DEV uint32_t resolve_pos(const DIndex &ix, uint64_t pos);
 enum : int { W_IDLE = 0, W_FETCH = 1, W_STEP = 2, W_SAMPLE = 3 };
 enum : int { WALK_BATCH = 0, WALK_TABLE16 = 1, WALK_TABLE32 = 2 };    // rows of a batch -> rowRef | every 2^genShift-th row -> u16 / u32 table
 
@@ -2711,8 +2712,13 @@ CF_DEV void walk2_body(const DIndex &ix, const DBatch &b) {
             if (chk) { const uint64_t blk = row >> ix.boundShift; bits = (ix.boundBits[blk >> 5] >> (blk & 31)) & 1u; }
         }
         // ---- processing
-        if (mode == W_FETCH) { row = rv; stepsHere = 0; classify(row); }
-        else if (mode == W_SAMPLE) { if (sub == 0) put(item, samp); mode = W_IDLE; }
+        if (mode == W_FETCH) {
+            if (MODE == WALK_BATCH && (rv & kRowIsPos)) {     // a hit in its position form: answered from the position, as walk3_body does (no step is counted)
+                const uint32_t ref = resolve_pos(ix, rv & ~kRowIsPos);
+                if (sub == 0) put(item, ref);
+                mode = W_IDLE;
+            } else { row = rv; stepsHere = 0; classify(row); }
+        } else if (mode == W_SAMPLE) { if (sub == 0) put(item, samp); mode = W_IDLE; }
         else if (mode == W_STEP) {
             bool resolved = false;
             if (chk && bits) {                                // rare: the row may be a genome-boundary row (.4.cf)

@@ -672,6 +672,31 @@ cf_status cf_debug_scan(int device, int mode, const uint32_t *in, uint64_t n, ui
 /* random 128-byte-side read bandwidth of the device over the resident sides
  * (the roofline denominator of SURVEY.md §8d): GB/s over `n_loads` loads. */
 cf_status cf_debug_random_read_gbps(cf_index *, uint64_t n_loads, int dependent_steps, double *gbps);
+/* Which kernels the slot's last batch was launched with (host-side bookkeeping of the launches, nothing is read from the
+ * device): what a test that forces a kernel variant (cf_knobs.hpp) proves its variant from.  Valid once the batch is finished. */
+enum { CF_SEARCH_NONE = 0, CF_SEARCH_WORDS = 1 /* k_search */, CF_SEARCH_SIDES = 2 /* k_search2, two lanes per chain */,
+       CF_SEARCH_PLANES = 3 /* k_search2_l1 */, CF_SEARCH_PLANES_LAZY1 = 4, CF_SEARCH_PLANES_LAZY2 = 5,
+       CF_SEARCH_MULTI = 6 /* k_search2_l1, small ranges against the text */ };
+typedef struct cf_launch_record {
+    int32_t  search_form;      /* CF_SEARCH_* */
+    uint32_t rec_words;        /* 64-bit words of a strand record (4 / 6 / 8), 0: none (k_search) */
+    uint32_t search_blocks;    /* blocks of the search kernel's grid */
+    int32_t  walk_version;     /* 3: k_walk3, 2: k_walk2, 0: no row was emitted or walked (direct references) */
+    int32_t  post_fast;        /* the common-case post kernel ran in front of the general one */
+    uint32_t post_cap_hits;    /* hit records per lane of the general post kernel's LDS scratch (0: none) */
+    int32_t  score_fast;       /* the common-case score kernel ran in front of the general one */
+    uint32_t score_cap_rows;   /* planned rows per query the general score kernel's LDS scratch holds (0: none) */
+    uint32_t score_sparse;     /* every score_sparse-th lane of it works */
+    uint32_t count_slot_bits;  /* log2 of the LDS slots of k_count / k_kreport */
+    int32_t  count_direct;     /* ... which are direct-mapped (every taxon has a slot of its own) */
+    int32_t  direct_refs, self_records, rev_words, lazy_hits;
+    int32_t  early_score;      /* the early score kernel ran beside the general post kernel */
+    int32_t  tail_stream;      /* 0, or the CF_TAIL_STREAM mode whose second stream was in use */
+    uint32_t passes;           /* passes of the row stage */
+    int32_t  pos_form;         /* the index resolves hits in their position form */
+    uint32_t pos_shift;        /* ... with 2^pos_shift positions per bucket */
+} cf_launch_record;
+cf_status cf_batch_debug_launch(const cf_batch *, cf_launch_record *);
 
 /* ------------------------------------------------------------ program entry
  * The whole classifier program as a call: the reference's own C symbol

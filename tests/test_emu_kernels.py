@@ -804,6 +804,36 @@ def test_index_without_its_sides_gives_the_same_rows(arch, name, search_version,
         e.close()
 
 
+@pytest.mark.parametrize("rate", [0, 3])
+@pytest.mark.parametrize("arch,name", [("synth_small", "k5"), ("synth_small", "r250_k5")])
+def test_chain_walk_kernel_takes_hits_in_the_position_form(arch, name, rate):
+    """walk2_body over the rows of a batch (CF_WALK_V=2) with hits in their position form among them: a marked row is a text
+    position, answered by resolve_pos as walk3_body does — not a suffix-array row to look up or step from (tests/test_gpu_variants.py
+    found the table read far outside with the sampled tables, and the wrong reference with the table at every row).  Rows as the
+    reference's, the steps counted as by the one-lane walk."""
+    from centrifuge_amd import capi
+    L = emu.lib()
+    d, cases = common.golden(arch)
+    c = [x for x in cases if x["name"] == name][0]
+    kw, fastq = common.case_kwargs(c["args"])
+    e = emu.Emu(os.path.join(d, "idx"))
+    names, qlens, seq, off, seeds, paired = reads.load([os.path.join(d, f) for f in c["reads"]], fastq)
+    want = open(os.path.join(d, c["tsv"])).read()
+    try:
+        L.emu_set_search_version(2); L.emu_set_direct_refs(0)
+        assert L.emu_planify(e.h, 1) == 1 and L.emu_textify(e.h, rate) == 1 and L.emu_densify(e.h, rate) >= 0 and L.emu_posify(e.h, 1) == 1
+        ops = {}
+        for wv in (3, 2):
+            L.emu_set_walk_version(wv)
+            ops[wv] = capi.OpCounts()
+            rows, n_rows, score2 = e.classify(seq, off, seeds, paired=paired, ops=ops[wv], **kw)
+            assert reads.format_tsv(e.seqid, names, qlens, rows, n_rows, score2) == want, wv
+        assert ops[2].n_pos_hits == ops[3].n_pos_hits > 0 and ops[2].n_walk == ops[3].n_walk
+    finally:
+        L.emu_set_walk_version(3); L.emu_set_direct_refs(1)
+        e.close()
+
+
 @pytest.mark.parametrize("arch,name", [("synth_small", "k5"), ("synth_small", "k1"), ("synth_small", "pe_k1"), ("synth_small", "r250_k5"), ("synth_small", "genus"), ("example", "default")])
 def test_references_straight_from_the_table_give_the_same_rows(arch, name):
     """DBatch::directRefs: with the resolve table at every row the common-case score kernel reads a row's reference from the
