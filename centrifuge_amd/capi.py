@@ -49,7 +49,8 @@ class LaunchRecord(C.Structure):
                 ("post_fast", C.c_int32), ("post_cap_hits", C.c_uint32), ("score_fast", C.c_int32), ("score_cap_rows", C.c_uint32),
                 ("score_sparse", C.c_uint32), ("count_slot_bits", C.c_uint32), ("count_direct", C.c_int32),
                 ("direct_refs", C.c_int32), ("self_records", C.c_int32), ("rev_words", C.c_int32), ("lazy_hits", C.c_int32),
-                ("early_score", C.c_int32), ("tail_stream", C.c_int32), ("passes", C.c_uint32), ("pos_form", C.c_int32), ("pos_shift", C.c_uint32)]
+                ("early_score", C.c_int32), ("tail_stream", C.c_int32), ("passes", C.c_uint32), ("pos_form", C.c_int32), ("pos_shift", C.c_uint32),
+                ("split_sinks", C.c_uint32)]
 
     def as_dict(self):
         d = {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -117,6 +118,19 @@ class BgzfReads(C.Structure):
 class BgzfInfo(C.Structure):
     """cf_bgzf_info of include/centrifuge_amd.h"""
     _fields_ = [("tail", C.c_void_p), ("tail_bytes", C.c_uint64), ("inflated_bytes", C.c_uint64), ("corrupt", C.c_uint32), ("bad_member", C.c_uint32)]
+
+
+SPLIT_UN, SPLIT_AL = 1, 2        # CF_SPLIT_* of include/centrifuge_amd.h
+
+
+class SplitSink(C.Structure):
+    """cf_split_sink"""
+    _fields_ = [("text", C.c_void_p), ("n_bytes", C.c_uint64), ("plain_bytes", C.c_uint64), ("n_records", C.c_uint64)]
+
+
+class SplitText(C.Structure):
+    """cf_split_text: un / un mate 1, un mate 2, al / al mate 1, al mate 2"""
+    _fields_ = [("sink", SplitSink * 4)]
 
 
 class ResultsText(C.Structure):
@@ -278,6 +292,8 @@ def lib():
         "cf_bgzf_eof": (None, [vp]), "cf_bgzf_deflate_host": (i32, [cp, u64, vp, u64, C.POINTER(u64)]),
         "cf_text_column_of": (C.c_int32, [cp]), "cf_batch_set_text_columns": (i32, [vp, vp, u32]),
         "cf_batch_set_text_trim": (i32, [vp, u32, u32]), "cf_batch_set_text_skip": (i32, [vp, u64]),
+        "cf_batch_set_text_split": (i32, [vp, u32, i32]), "cf_batch_wait_text_split": (i32, [vp, C.POINTER(SplitText)]),
+        "cf_batch_split_ms": (i32, [vp, C.POINTER(C.c_float)]),
         "cf_counts_get_single": (i32, [vp, vp]),
         "cf_report_add_tuples": (i32, [vp, vp, u64]), "cf_report_adopt_device_tally": (i32, [vp, vp, vp, vp, u64]),
         "cf_batch_set_limits": (i32, [vp, u64, u64]),
@@ -784,6 +800,24 @@ class Slot:
         tuples = np.frombuffer(C.string_at(r.tuples, 4 * r.n_tuple_words), dtype=np.uint32).copy() if r.n_tuple_words else np.zeros(0, np.uint32)
         return members, n.value, tuples, {"n_queries": r.n_queries, "total_rows": r.total_rows, "planned_sa_rows": r.planned_sa_rows, "row_passes": r.row_passes,
                                           "slow_post": r.slow_post, "slow_score": r.slow_score}
+
+    def set_text_split(self, sinks, bgzf=False):
+        """the classes (SPLIT_UN | SPLIT_AL; 0: none) the slot's later batches' reads are written out by, as FASTQ records per printed
+        row; bgzf: each sink as BGZF members deflated on the device"""
+        _check(self.L.cf_batch_set_text_split(self.h, int(sinks), 1 if bgzf else 0))
+
+    def wait_text_split(self):
+        """after wait_text() / wait_text_bgzf(): the four sinks (un / un mate 1, un mate 2, al / al mate 1, al mate 2) as a list of
+        (bytes, plain_bytes, n_records)"""
+        r = SplitText()
+        _check(self.L.cf_batch_wait_text_split(self.h, C.byref(r)))
+        return [(C.string_at(k.text, k.n_bytes) if k.n_bytes else b"", int(k.plain_bytes), int(k.n_records)) for k in r.sink]
+
+    def split_ms(self):
+        """device ms of the split kernels of the last wait_text_split()"""
+        ms = C.c_float()
+        _check(self.L.cf_batch_split_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def kreport_ms(self):
         """k_kreport's time in the slot's last batch (cf_batch_kreport_ms)"""

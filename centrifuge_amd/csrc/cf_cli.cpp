@@ -6,6 +6,7 @@
 // the report file (centrifuge.cpp:3231-3319).  All classification work goes through
 // the C ABI of libcentrifuge_amd.so (include/centrifuge_amd.h); this file is host
 // plumbing: option parsing, read ingest, batching, formatting.
+#include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -57,6 +58,9 @@ struct Opts {
     int devInflate = 1;                                 // --device-inflate off | unpaired | all: which BGZF inputs are inflated on the device (0, 1, 2)
     std::string kreportFile;                            // --kreport-file: what centrifuge-kreport prints for this run's output, tallied on the device (cf_kreport_enable)
     bool outBgzf = false;                               // --out-bgzf: the classification output is one BGZF file (the device text path's blocks are deflated on the device)
+    // --un / --al / --un-conc / --al-conc (and their -gz forms): where the reads themselves go, by what became of them (empty: nowhere)
+    std::string splitPath[4];                           // un, al, un-conc, al-conc
+    bool splitGz[4] = {false, false, false, false};
     bool hostIo = false;                                // --host-io: the parser pool and the formatter threads for every input (no device text path)
     int smallRangeRows = 0;                             // --small-range-rows: cf_index_options::small_range_rows (0 = automatic, -1 = off)
     double hbmBudgetGb = 0;                             // --hbm-budget-gb: cf_index_options::hbm_budget_bytes (0 = what the device has free)
@@ -99,6 +103,11 @@ void usage(std::FILE *f) {
         " Output:  -S <file>  --report-file <file> (centrifuge_report.tsv)  --no-abundance  --tab-fmt-cols <c,..>  --out-fmt tab|sam  -t/--time\n"
         "          --kreport-file <file> (the Kraken-style report `centrifuge-kreport -x <cf-idx> <output>` prints for this run's output, tallied on\n"
         "             the device: no second pass over the text.  Two neighbouring reads of one name are refused: exit status 1, no file)\n"
+        "          --un <path> / --al <path> (unpaired reads without / with an assignment, as FASTQ records — one per ROW of the output, so a\n"
+        "          read with three assignments is written three times, as the reference's wrapper writes it)  --un-conc / --al-conc <path>\n"
+        "          (the same for pairs, mate 1 and mate 2 in two files: every % of the name becomes 1 / 2, else x.fq becomes x.1.fq / x.2.fq,\n"
+        "          else .1 / .2 is appended; a directory takes un-seqs, al-seqs, un-conc-mate.1 ...)  --un-gz --al-gz --un-conc-gz --al-conc-gz\n"
+        "          (the same files as BGZF; blocks on the device text path are split and deflated there)\n"
         "          --out-bgzf (the classification output — -S or stdout: header line, rows, --separator markers, the SAM form — as one BGZF\n"
         "          file, the blocked gzip of bgzip / htslib, that inflates to the bytes the run prints without the flag; rows formatted on\n"
         "          the device are deflated there and cross the link compressed, the rest is deflated by zlib; the report stays plain)\n"
@@ -215,7 +224,18 @@ Opts parse(int argc, const char **argv) {
         else if (a == "--batch") o.batch = std::max<uint64_t>(1, std::strtoull(val().c_str(), nullptr, 10));
         else if (a == "--reorder" || a == "--mm" || a == "--non-deterministic" || a == "--qc-filter" || a == "--phred33" ||
                  a == "--ignore-quals" || a == "--nofw" || a == "--norc" || a == "--no-1mm-upfront") {}      // accepted, no effect on this path
-        else if (a == "--min-totallen" || a == "--met-file" || a == "--met" || a == "--un" || a == "--al") (void)val();
+        else if (a == "--min-totallen" || a == "--met-file" || a == "--met") (void)val();
+        else if (a.rfind("--un", 0) == 0 || a.rfind("--al", 0) == 0) {
+            // centrifuge:212-227: --un / --al / --un-conc / --al-conc <path>, -gz: compressed (here: BGZF); -bz2 is not offered
+            std::string k = a.substr(2);
+            bool gz = false;
+            if (k.size() > 4 && k.compare(k.size() - 4, 4, "-bz2") == 0) die("centrifuge-class: option '" + a + "' is not supported: use '" + a.substr(0, a.size() - 4) + "-gz'");
+            if (k.size() > 3 && k.compare(k.size() - 3, 3, "-gz") == 0) { gz = true; k.resize(k.size() - 3); }
+            const int which = k == "un" ? 0 : k == "al" ? 1 : k == "un-conc" ? 2 : k == "al-conc" ? 3 : -1;
+            if (which < 0) die("centrifuge-class: unrecognized option '" + a + "'");
+            o.splitPath[which] = val(); o.splitGz[which] = gz;
+            if (o.splitPath[which].empty()) die("option " + a + " requires a file name");
+        }
         else if (a == "-h" || a == "--help") { usage(stdout); throw CliExit("", 0); }
         else if (a == "--version") { std::puts("centrifuge-class (centrifuge_amd, MI355X-native path; Centrifuge 1.0.4 compatible)"); throw CliExit("", 0); }
         else if (a.size() > 1 && a[0] == '-' && a != "-") die("centrifuge-class: unrecognized option '" + a + "'");
@@ -419,6 +439,10 @@ struct GpuThread {
     std::string zHead2;                             // ... of the second file of mates
     std::string tabText;                            // a tabbed block parsed on the host: the text of its runs of pairs / unpaired reads, one behind the other
     std::vector<char> zText;                        // --out-bgzf: a block the host formatted, deflated (cf_bgzf_deflate_host)
+    std::string spText[6];                          // --un / --al ...: the records of a block the host parsed, per file
+    std::vector<char> spZ[6];                       // ... and a sink's text deflated here (a -gz file beside a plain one)
+    double splitMs = 0;                             // k_split_*'s ms over this thread's batches (HIP events)
+    uint64_t splitBatches = 0;
     double krMs = 0;                                // --kreport-file: k_kreport's ms over this thread's batches (HIP events)
     uint64_t krBatches = 0;
     uint64_t zOutText = 0, zOutBytes = 0, zOutBatches = 0;   // ... and the batches deflated on the device: their text, their members, k_deflate's ms
@@ -470,6 +494,7 @@ struct Runner {
     ~Runner() {                                     // error paths leave through here as well
         try { waitWrite(); } catch (...) {}          // (a run that ends on an error: the writer must be done with the file before it is closed)
         if (out && out != stdout) std::fclose(out);
+        for (auto &F : sp) if (F.fd >= 0) ::close(F.fd);
         if (rep) cf_report_destroy(rep);
         for (auto &g : gts) { if (g.slot) cf_batch_destroy(g.slot); if (g.rep) cf_report_destroy(g.rep); if (g.stream) cf_stream_destroy(g.stream); if (g.tin) cf_host_free(g.tin); }
         for (cf_report *r : fmtReps) if (r) cf_report_destroy(r);
@@ -798,6 +823,167 @@ struct Runner {
         if (std::fwrite(zOut.data(), 1, zOut.size(), out) != zOut.size()) die("error writing the classification output");
     }
 
+    // ---- --un / --al / --un-conc / --al-conc: the reads themselves, one FASTQ record per printed row (the reference's wrapper script,
+    // centrifuge:855-931, makes them from the readSeq / readQual columns).  Six files: un, al, un-conc mate 1 / 2, al-conc mate 1 / 2.
+    // A block of the device text path has its records made on the device (cf_batch_wait_text_split) and every GPU thread writes them
+    // at the place the file's own chain hands out in block order, as the classification output's text is written; everything else —
+    // batches of the parser pool, blocks outside the plain form — is made by splitRange and written in output order.
+    struct SplitFile {
+        int fd = -1;
+        bool gz = false, regular = false;
+        uint64_t base = 0, bytes = 0;               // where the input in hand starts; text bytes (before any deflate) so far
+        std::string path;
+        OrderedSum chain;
+    };
+    SplitFile sp[6];
+    bool splitOn = false;
+    static int splitFileOf(bool paired, uint32_t sink) { return paired ? 2 + (int)sink : sink == 0 ? 0 : sink == 2 ? 1 : -1; }
+    void splitOpen() {
+        auto isDir = [](const std::string &p) { struct stat sb; return ::stat(p.c_str(), &sb) == 0 && S_ISDIR(sb.st_mode); };
+        auto samePath = [](const std::string &a, const std::string &b) {
+            if (a == b) return true;
+            struct stat sa, sb;                          // (b is not made yet: a is, and two names of one file share its inode)
+            return ::stat(a.c_str(), &sa) == 0 && ::stat(b.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino && S_ISREG(sa.st_mode);
+        };
+        auto openOne = [&](int f, const std::string &path, bool gz, const char *opt) {
+            // (two options that name one file would truncate and overwrite each other)
+            for (int g = 0; g < 6; g++) if (sp[g].fd >= 0 && samePath(sp[g].path, path)) die(std::string("Error: --") + opt + " and another of --un / --al / --un-conc / --al-conc name the same file '" + path + "'");
+            sp[f].path = path; sp[f].gz = gz;
+            sp[f].fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+            if (sp[f].fd < 0) die(std::string("Could not open --") + opt + " output file '" + path + "'");
+            struct stat sb;
+            sp[f].regular = ::fstat(sp[f].fd, &sb) == 0 && S_ISREG(sb.st_mode);
+            splitOn = true;
+        };
+        static const char *const kOpt[4] = {"un", "al", "un-conc", "al-conc"};
+        for (int w = 0; w < 4; w++) {
+            const std::string &p = o.splitPath[w];
+            if (p.empty()) continue;
+            const bool dir = isDir(p);
+            if (w < 2) { openOne(w, dir ? p + "/" + kOpt[w] + "-seqs" : p, o.splitGz[w], kOpt[w]); continue; }
+            // centrifuge:730-749: every % becomes the mate's number, else the number goes in front of the extension, else behind the name
+            const size_t slash = dir ? std::string::npos : p.rfind('/');
+            const std::string where = dir ? p + "/" : slash == std::string::npos ? std::string() : p.substr(0, slash + 1);
+            const std::string name = dir ? std::string(kOpt[w]) + "-mate" : slash == std::string::npos ? p : p.substr(slash + 1);
+            std::string n[2] = {name, name};
+            for (int m = 0; m < 2; m++) {
+                const char digit = (char)('1' + m);
+                const size_t dot = n[m].rfind('.');
+                if (n[m].find('%') != std::string::npos) std::replace(n[m].begin(), n[m].end(), '%', digit);
+                else if (dot != std::string::npos) n[m].insert(dot + 1, std::string(1, digit) + ".");
+                else n[m] += std::string(".") + digit;
+            }
+            for (int m = 0; m < 2; m++) openOne(2 + 2 * (w - 2) + m, where + n[m], o.splitGz[w], kOpt[w]);
+        }
+    }
+    // the classes a batch of that kind can feed (CF_SPLIT_*)
+    uint32_t splitSinksFor(bool paired) const {
+        if (!splitOn) return 0;
+        return (sp[paired ? 2 : 0].fd >= 0 ? CF_SPLIT_UN : 0u) | (sp[paired ? 4 : 1].fd >= 0 ? CF_SPLIT_AL : 0u);
+    }
+    struct SplitPieces { const char *p[6] = {}; uint64_t n[6] = {}, plain[6] = {}; };
+    // a batch whose text was just waited for (cf_batch_wait_text): its reads split on the device — deflated there as well when every
+    // file the batch feeds is a -gz one, else by zlib here
+    void splitDevice(GpuThread &g, bool paired, SplitPieces &pc) {
+        const uint32_t sinks = splitSinksFor(paired);
+        if (!sinks) return;
+        bool allGz = true;
+        for (uint32_t s = 0; s < 4; s++) { const int f = splitFileOf(paired, s); if (f >= 0 && sp[f].fd >= 0) allGz = allGz && sp[f].gz; }
+        CF_TRY(cf_batch_set_text_split(g.slot, sinks, allGz ? 1 : 0));
+        cf_split_text sx{};
+        CF_TRY(cf_batch_wait_text_split(g.slot, &sx));
+        float ms = 0;
+        CF_TRY(cf_batch_split_ms(g.slot, &ms));
+        g.splitMs += ms; g.splitBatches++;
+        for (uint32_t s = 0; s < 4; s++) {
+            const int f = splitFileOf(paired, s);
+            if (f < 0 || sp[f].fd < 0) continue;
+            pc.p[f] = sx.sink[s].text; pc.n[f] = sx.sink[s].n_bytes; pc.plain[f] = sx.sink[s].plain_bytes;
+            if (sp[f].gz && !allGz && pc.n[f]) { bgzfHost(pc.p[f], pc.n[f], g.spZ[f]); pc.p[f] = g.spZ[f].data(); pc.n[f] = g.spZ[f].size(); }
+        }
+    }
+    // the records of queries [q0, q1) of a batch the host parsed, as formatRange would print their readID, readSeq and readQual
+    void splitRange(const Batch &b, const std::vector<uint32_t> &nRows, uint64_t q0, uint64_t q1, std::string *to) const {
+        const int per = b.paired ? 2 : 1;
+        const ReadSoA &r = b.r;
+        std::string rec;
+        for (uint64_t q = q0; q < q1; q++) {
+            const size_t ra = q * per;
+            const uint32_t n = std::max<uint32_t>(1, nRows[q]), cls = nRows[q] ? 1u : 0u;
+            for (int m = 0; m < per; m++) {
+                const int f = b.paired ? 2 + 2 * (int)cls + m : (int)cls;
+                if (sp[f].fd < 0) continue;
+                rec.assign(1, '@');
+                appendReadId(rec, r.names.data() + r.nameOff[ra], r.nameOff[ra + 1] - r.nameOff[ra]);
+                rec.push_back('\n');
+                appendSeq(rec, r, ra + m);
+                rec += "\n+\n";
+                appendQual(rec, r, ra + m);
+                rec.push_back('\n');
+                for (uint32_t i = 0; i < n; i++) to[f] += rec;
+            }
+        }
+    }
+    // ... of a block of the text path that the host parsed: added to the thread's strings (a tabbed block is several batches)
+    void splitHostBlock(const Batch &b, GpuThread &g) { if (splitOn && b.nq) splitRange(b, b.nRows, 0, b.nq, g.spText); }
+    void splitHostPieces(GpuThread &g, SplitPieces &pc) {
+        for (int f = 0; f < 6; f++) {
+            if (sp[f].fd < 0) continue;
+            pc.p[f] = g.spText[f].data(); pc.n[f] = pc.plain[f] = g.spText[f].size();
+            if (sp[f].gz && pc.n[f]) { bgzfHost(pc.p[f], pc.n[f], g.spZ[f]); pc.p[f] = g.spZ[f].data(); pc.n[f] = g.spZ[f].size(); }
+        }
+    }
+    void splitWriteAt(SplitFile &F, const char *p, uint64_t n, uint64_t at) {
+        while (n) {
+            const ssize_t w = F.regular ? ::pwrite(F.fd, p, n, (off_t)at) : ::write(F.fd, p, n);
+            if (w < 0) { if (errno == EINTR) continue; die("error writing " + F.path); }
+            p += w; n -= (uint64_t)w; at += (uint64_t)w;
+        }
+    }
+    // a block of the text path (every one of an input, in whatever order they get here): its pieces at their places in the files
+    void splitWriteBlock(uint64_t tIdx, const SplitPieces &pc) {
+        if (!splitOn) return;
+        for (int f = 0; f < 6; f++) {
+            SplitFile &F = sp[f];
+            if (F.fd < 0) continue;
+            const uint64_t at = F.chain.enter(tIdx);
+            if (F.regular) { F.chain.leave(pc.n[f]); splitWriteAt(F, pc.p[f], pc.n[f], F.base + at); }
+            else { try { splitWriteAt(F, pc.p[f], pc.n[f], 0); } catch (...) { F.chain.leave(pc.n[f]); throw; } F.chain.leave(pc.n[f]); }
+            if (pc.plain[f]) { std::lock_guard<std::mutex> lk(F.chain.mu); F.bytes += pc.plain[f]; }
+        }
+    }
+    // an input starts on / has gone through the text path (no block of it is in flight)
+    void splitBegin() { for (auto &F : sp) F.chain.reset(); }
+    void splitEnd() { for (auto &F : sp) { F.base += F.chain.sum; F.chain.reset(); } }
+    void splitFail() { for (auto &F : sp) F.chain.fail(); }
+    // a batch of the output stage (one caller at a time, in output order)
+    std::string spEmit[6];
+    std::vector<char> spEmitZ;
+    void splitEmit(const Batch &b) {
+        if (!splitOn) return;
+        for (auto &t : spEmit) t.clear();
+        splitRange(b, b.nRows, 0, b.nq, spEmit);
+        for (int f = 0; f < 6; f++) {
+            SplitFile &F = sp[f];
+            if (F.fd < 0 || spEmit[f].empty()) continue;
+            const char *p = spEmit[f].data();
+            uint64_t n = spEmit[f].size();
+            F.bytes += n;
+            if (F.gz) { bgzfHost(p, n, spEmitZ); p = spEmitZ.data(); n = spEmitZ.size(); }
+            splitWriteAt(F, p, n, F.base);
+            F.base += n;
+        }
+    }
+    void splitClose() {
+        for (auto &F : sp) {
+            if (F.fd < 0) continue;
+            if (F.gz) { uint8_t eof[28]; cf_bgzf_eof(eof); splitWriteAt(F, reinterpret_cast<const char *>(eof), 28, F.base); F.base += 28; }
+            const int fd = F.fd;
+            F.fd = -1;
+            if (::close(fd) != 0) die("error closing " + F.path);
+        }
+    }
+
     // n bytes at `at` of the output file through a mapping of that stretch; false = the file cannot be mapped (the caller writes)
     bool copyIntoFile(const char *text, uint64_t n, uint64_t at) {
         if (n == 0) return true;
@@ -902,6 +1088,7 @@ struct Runner {
         if (base + nReads >= o.upto) uptoReached = true;
         const char *text = "";
         uint64_t nText = 0;
+        SplitPieces pieces;
         if (take == 0) { /* (past -u: nothing of this block is printed) */ }
         else if (!onHost) {
             if (take < nReads) {                                        // the block -s ends in or -u ends in: once more, those reads only
@@ -924,12 +1111,14 @@ struct Runner {
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
             krDevice(b, g);
+            splitDevice(g, per == 2, pieces);
             text = res.text; nText = res.n_bytes;
             b.nq = res.n_queries;
             textBatches++; g.textBlocks++;
             lap(g.tm.report);
         } else {
             g.hostBlocks++;
+            for (auto &t : g.spText) t.clear();
             ReadSoA tabSrc;
             if (tab) std::swap(tabSrc, b.r);
             else if (mates || take < nReads || b.r.hasEmptyName()) {
@@ -995,6 +1184,7 @@ struct Runner {
                 std::memcpy(ob.room(s.size()), s.data(), s.size());
                 ob.len = s.size();
             }
+            splitHostBlock(b, g);
             lap(g.tm.format);
             };
             if (!tab) { hostRun(mates); text = hostOut[gi]->p.get(); nText = hostOut[gi]->len; }
@@ -1021,11 +1211,13 @@ struct Runner {
                 text = g.tabText.data(); nText = g.tabText.size();
             }
             if (o.outBgzf) { bgzfHost(text, nText, g.zText); text = g.zText.data(); nText = g.zText.size(); }
+            if (splitOn) splitHostPieces(g, pieces);
         }
         // the block's place in the output: behind the blocks before it
         const uint64_t at = outChain.enter(b.tIdx);
         if (outRegular) { outChain.leave(nText); if (!(outMap && copyIntoFile(text, nText, outBase + at))) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
         else { try { writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
+        splitWriteBlock(b.tIdx, pieces);
         lap(g.tm.write);
         b.nq = 0;                                          // (the output stage has nothing left to do for this batch)
     }
@@ -1080,6 +1272,7 @@ struct Runner {
         if (!skip && base + nReads >= o.upto) uptoReached = true;
         const char *text = "";
         uint64_t nText = 0;
+        SplitPieces pieces;
         if (take) {
             if (take < nReads) {                                        // the run -s ends in or -u ends in: once more, those reads only
                 in.max_reads = upTo < nReads ? take : 0;
@@ -1101,6 +1294,7 @@ struct Runner {
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
             krDevice(b, g);
+            splitDevice(g, info.paired != 0, pieces);
             text = res.text; nText = res.n_bytes;
             textBatches++; g.textBlocks++;
             lap(g.tm.report);
@@ -1109,6 +1303,7 @@ struct Runner {
         const uint64_t at = outChain.enter(b.tIdx);
         if (outRegular) { outChain.leave(nText); if (nText) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
         else { try { if (nText) writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
+        splitWriteBlock(b.tIdx, pieces);
         lap(g.tm.write);
         b.nq = 0;
     }
@@ -1170,6 +1365,7 @@ struct Runner {
         if (!skip && base + nPairs >= o.upto) uptoReached = true;
         const char *text = "";
         uint64_t nText = 0;
+        SplitPieces pieces;
         if (take) {
             if (take < nPairs) {                                        // the run -s ends in or -u ends in: once more, those pairs only
                 in1.max_reads = in2.max_reads = upTo < nPairs ? take : 0;
@@ -1191,6 +1387,7 @@ struct Runner {
             lap(g.tm.classify);
             if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
             krDevice(b, g);
+            splitDevice(g, true, pieces);
             text = res.text; nText = res.n_bytes;
             textBatches++; g.textBlocks++;
             lap(g.tm.report);
@@ -1199,6 +1396,7 @@ struct Runner {
         const uint64_t at = outChain.enter(b.tIdx);
         if (outRegular) { outChain.leave(nText); if (nText) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
         else { try { if (nText) writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
+        splitWriteBlock(b.tIdx, pieces);
         lap(g.tm.write);
         b.nq = 0;
     }
@@ -1270,6 +1468,7 @@ struct Runner {
         for (const cf_status st_ : tallySt) CF_TRY(st_);
         lap(tm.format);
         waitWrite();                                     // the batch before this one is in the file (and its buffers are free again)
+        splitEmit(b);
         if (defaultCols) {
             // this batch's text goes out while the next one is formatted into the other set of buffers
             std::vector<OutBuf> *set = &fmtBufs;
@@ -1488,6 +1687,7 @@ int run(int argc, const char **argv) {
             R.out = std::fopen(o.outFile.c_str(), "w+b");         // (readable as well: the device text path maps the file)
             if (!R.out) die("Error: Could not open alignment output file " + o.outFile);
         }
+        R.splitOpen();
         // header (centrifuge.cpp:2985-2992); none under --out-fmt sam
         if (!o.samFormat) {
             std::string h;
@@ -1536,7 +1736,7 @@ int run(int argc, const char **argv) {
             }
         } catch (const std::exception &e) {
             { std::lock_guard<std::mutex> lk(mu); if (workerError.empty()) workerError = e.what(); }
-            R.readChain.fail(); R.outChain.fail(); R.tailChain.fail();           // (threads waiting for this one's block must not wait for ever)
+            R.readChain.fail(); R.outChain.fail(); R.tailChain.fail(); R.splitFail();           // (threads waiting for this one's block must not wait for ever)
         }
         { std::lock_guard<std::mutex> lk(mu); gpuRunning--; }
         cv.notify_all();
@@ -1612,7 +1812,7 @@ int run(int argc, const char **argv) {
                 R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
                 R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
                 R.outMap = R.outRegular && cfamd::cf_knob("CF_CLI_MAP_OUTPUT") && std::atoi(cfamd::cf_knob("CF_CLI_MAP_OUTPUT")) && !o.outBgzf;
-                R.readChain.reset(); R.outChain.reset(); R.uptoReached = false;
+                R.readChain.reset(); R.outChain.reset(); R.splitBegin(); R.uptoReached = false;
                 const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(32u << 20);
                 void *m1 = ::mmap(nullptr, (size_t)fs1, PROT_READ, MAP_SHARED, fd1, 0), *m2 = ::mmap(nullptr, (size_t)fs2, PROT_READ, MAP_SHARED, fd2, 0);
                 struct Unmap { void *a, *b; size_t na, nb; ~Unmap() { if (a != MAP_FAILED) ::munmap(a, na); if (b != MAP_FAILED) ::munmap(b, nb); } } unmap{m1, m2, (size_t)fs1, (size_t)fs2};
@@ -1666,6 +1866,7 @@ int run(int argc, const char **argv) {
                     R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
                 }
                 if (aborted || !drain()) { aborted = true; break; }
+                R.splitEnd();
                 if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
                 if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
                 if (!changeOver || R.uptoReached) continue;
@@ -1690,7 +1891,7 @@ int run(int argc, const char **argv) {
                 R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
                 R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
                 R.outMap = false;
-                R.readChain.reset(); R.outChain.reset(); R.tailChain.reset(); R.uptoReached = false;
+                R.readChain.reset(); R.outChain.reset(); R.splitBegin(); R.tailChain.reset(); R.uptoReached = false;
                 R.zTail.clear(); R.zTail2.clear(); R.zStopped = false; R.zResumeHead.clear(); R.zResumeHead2.clear(); R.zWhy.clear(); R.zCons = R.zCons2 = 0;
                 const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
                 void *zm1 = ::mmap(nullptr, (size_t)zs1, PROT_READ, MAP_SHARED, zfd1, 0);
@@ -1739,6 +1940,7 @@ int run(int argc, const char **argv) {
                     { std::lock_guard<std::mutex> lk(R.tailChain.mu); if (R.zStopped) break; }       // (no run behind a refused one is of use)
                 }
                 if (aborted || !drain()) { aborted = true; break; }
+                R.splitEnd();
                 if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
                 if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
                 if (R.uptoReached || (!R.zStopped && pos[0] >= zs1 && pos[1] >= zs2)) continue;
@@ -1766,7 +1968,7 @@ int run(int argc, const char **argv) {
                 R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
                 R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
                 R.outMap = R.outRegular && cfamd::cf_knob("CF_CLI_MAP_OUTPUT") && std::atoi(cfamd::cf_knob("CF_CLI_MAP_OUTPUT")) && !o.outBgzf;
-                R.readChain.reset(); R.outChain.reset(); R.uptoReached = false;
+                R.readChain.reset(); R.outChain.reset(); R.splitBegin(); R.uptoReached = false;
                 const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
                 uint64_t pos = 0, idx = 0;
                 while (pos < fsize && !R.uptoReached) {
@@ -1786,6 +1988,7 @@ int run(int argc, const char **argv) {
                 }
                 if (aborted || !drain()) { aborted = true; break; }
                 // the output continues behind this input's text
+                R.splitEnd();
                 if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
                 if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
                 continue;
@@ -1804,7 +2007,7 @@ int run(int argc, const char **argv) {
                 R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
                 R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
                 R.outMap = false;
-                R.readChain.reset(); R.outChain.reset(); R.tailChain.reset(); R.uptoReached = false;
+                R.readChain.reset(); R.outChain.reset(); R.splitBegin(); R.tailChain.reset(); R.uptoReached = false;
                 R.zTail.clear(); R.zStopped = false; R.zResumeHead.clear(); R.zWhy.clear();
                 const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
                 void *zm = ::mmap(nullptr, (size_t)fsize, PROT_READ, MAP_SHARED, fd, 0);
@@ -1837,6 +2040,7 @@ int run(int argc, const char **argv) {
                     { std::lock_guard<std::mutex> lk(R.tailChain.mu); if (R.zStopped) break; }       // (no run behind a refused one is of use)
                 }
                 if (aborted || !drain()) { aborted = true; break; }
+                R.splitEnd();
                 if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
                 if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
                 if (R.uptoReached || (!R.zStopped && pos >= fsize)) continue;
@@ -2057,6 +2261,13 @@ int run(int argc, const char **argv) {
             std::fprintf(stderr, "Device deflate: %llu batch(es), %llu bytes of text into %llu bytes of BGZF members on the device, k_deflate %.2f ms in all (HIP events)\n",
                          (unsigned long long)zn, (unsigned long long)zt, (unsigned long long)zb, zms);
         }
+        if (R.splitOn) {
+            double ms = 0; uint64_t nb = 0, bytes = 0;
+            for (const auto &t : R.gts) { ms += t.splitMs; nb += t.splitBatches; }
+            for (const auto &F : R.sp) bytes += F.bytes;
+            std::fprintf(stderr, "Read split: %llu bytes of FASTQ records into the --un / --al files; %llu batch(es) split on the device, k_split_size + sums + k_split_write %.3f ms in all, %.4f ms per batch (HIP events)\n",
+                         (unsigned long long)bytes, (unsigned long long)nb, ms, nb ? ms / (double)nb : 0.0);
+        }
         if (!o.kreportFile.empty()) {
             double ms = 0; uint64_t nb = 0;
             for (const auto &t : R.gts) { ms += t.krMs; nb += t.krBatches; }
@@ -2078,6 +2289,7 @@ int run(int argc, const char **argv) {
     }
     if (R.out != stdout) { std::FILE *f = R.out; R.out = stdout; if (std::fclose(f) != 0) die("error closing the classification output"); }
     else std::fflush(stdout);
+    R.splitClose();
     if (!o.separator && !o.reportFile.empty()) R.writeReport(R.finishReport(), o.reportFile, hms);   // one coalesced report (centrifuge.cpp:3231-3319)
     int rc = 0;
     if (!o.kreportFile.empty()) {

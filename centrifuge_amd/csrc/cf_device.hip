@@ -315,6 +315,8 @@ __global__ void __launch_bounds__(256) k_fmt_size(DTextFmt f) { fmt_size_body(f,
 __global__ void __launch_bounds__(256) k_fmt_write(DTextFmt f) { fmt_write_body(f, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_cols_size(DTextFmt f, TextCols pc) { fmt_cols_size_body(f, pc, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_cols_write(DTextFmt f, TextCols pc) { fmt_cols_write_body(f, pc, cf_global_thread()); }
+__global__ void __launch_bounds__(256) k_split_size(DTextSplit d) { split_size_body(d, cf_global_thread()); }
+__global__ void __launch_bounds__(256) k_split_write(DTextSplit d) { split_write_body(d, cf_global_thread()); }
 template <int G, bool WRITE>
 __global__ void __launch_bounds__(256) k_restore(DIndex ix, DRestore r) { restore_body<G, WRITE>(ix, r); }
 __global__ void __launch_bounds__(256) k_restore_rank(const uint64_t *sumIn, const uint32_t *nextIn, uint64_t *sumOut, uint32_t *nextOut, uint32_t nElem) {
@@ -524,6 +526,24 @@ struct cf_batch {
     bool textBgzf = false;
     uint64_t textPlainBytes = 0;
     hipEvent_t evDef[2] = {};                // around k_deflate (cf_batch_deflate_ms)
+    // cf_batch_set_text_split / cf_batch_wait_text_split: the classes the slot's batches are split into, the sinks' sizes per query, their
+    // sums, their text (or members) on the device and in pinned memory
+    uint32_t splitSinks = 0;
+    bool splitBgzf = false, splitDone = false;
+    DevBuf<uint32_t> spSize[kSplitSinks];
+    DevBuf<uint64_t> spOff[kSplitSinks];
+    DevBuf<uint8_t> spOut[kSplitSinks];
+    PinBuf<uint8_t> hSpOut[kSplitSinks];
+    DevBuf<unsigned long long> spRec;
+    PinBuf<uint64_t> hSpTotal;               // per sink: bytes of text, records, bytes of the members
+    uint64_t spBytes[kSplitSinks] = {}, spPlain[kSplitSinks] = {}, spRecords[kSplitSinks] = {};
+    DevBuf<uint8_t> spZ[kSplitSinks];        // bgzf: a sink's members at their stride, their sizes and places (per sink: the sinks' deflates queue up without the host)
+    DevBuf<uint32_t> spZSize[kSplitSinks];
+    DevBuf<uint64_t> spZOff[kSplitSinks];
+    DevBuf<uint64_t> spTileA[kSplitSinks];
+    DevBuf<uint32_t> spTileC[kSplitSinks];
+    hipEvent_t evSplit[4] = {};              // around k_split_size + the sums, and around k_split_write (cf_batch_split_ms: the two stretches added)
+    float splitMs = 0;
     float deflateMs = 0;
     hipEvent_t evKr[2] = {};                 // around k_kreport of a batch's first pass (cf_batch_kreport_ms)
     bool krTimed = false;
@@ -566,7 +586,7 @@ struct cf_batch {
     hipEvent_t ev[10] = {};                  // 0..4 stage marks of classify, 5/6 plan, 7 done, 8 uploaded, 9 classified
     hipEvent_t evLate = nullptr;             // CF_TAIL_STREAM=2: the common-case score kernel is done, the tail may start
     bool evInit = false;
-    ~cf_batch() { for (auto &e : evDef) if (e) (void)hipEventDestroy(e); for (auto &e : evKr) if (e) (void)hipEventDestroy(e); if (evInit) { for (auto &e : ev) (void)hipEventDestroy(e); (void)hipEventDestroy(evLate); (void)hipEventDestroy(evPostFast); (void)hipEventDestroy(evPost); } if (tail) (void)hipStreamDestroy(tail); }
+    ~cf_batch() { for (auto &e : evDef) if (e) (void)hipEventDestroy(e); for (auto &e : evSplit) if (e) (void)hipEventDestroy(e); for (auto &e : evKr) if (e) (void)hipEventDestroy(e); if (evInit) { for (auto &e : ev) (void)hipEventDestroy(e); (void)hipEventDestroy(evLate); (void)hipEventDestroy(evPostFast); (void)hipEventDestroy(evPost); } if (tail) (void)hipStreamDestroy(tail); }
 };
 
 namespace {
@@ -2464,7 +2484,7 @@ cf_status cf_classify_async(cf_classifier *cl, cf_batch *bt, void *streamv) {
         HIP_OK(hipSetDevice(cl->ix->device));
         if (!bt->loaded) throw ArgError("no reads were uploaded into this slot");
         hipStream_t st = static_cast<hipStream_t>(streamv);
-        bt->rowsStay = false; bt->textDone = false;
+        bt->rowsStay = false; bt->textDone = false; bt->splitDone = false;
         if (!bt->planned) enqueuePlan(bt, st);
         enqueueClassify(bt, st);
     });
@@ -2479,7 +2499,7 @@ cf_status cf_batch_reclassify_async(cf_classifier *cl, cf_batch *bt, void *strea
         if (!bt->loaded) throw ArgError("no reads were uploaded into this slot");
         if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
         hipStream_t st = static_cast<hipStream_t>(streamv);
-        bt->rowsStay = false; bt->textDone = false;
+        bt->rowsStay = false; bt->textDone = false; bt->splitDone = false;
         enqueuePlan(bt, st);
         enqueueClassify(bt, st);
     });
@@ -2831,6 +2851,132 @@ static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_
 cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) { return waitText(bt, res, false, nullptr); }
 // ... as whole BGZF members, deflated on the device from the same text (cf_deflate.hpp): the text itself does not cross the link
 cf_status cf_batch_wait_text_bgzf(cf_batch *bt, cf_results_text *res, uint64_t *textBytes) { return waitText(bt, res, true, textBytes); }
+
+// The reads themselves, split by class (cf_textio.hpp "egress: the reads themselves"): sized, summed and written on the device from
+// what the batch left there — queries' bytes, readIDs in the uploaded block, packed bases, quality places —, behind the batch's text.
+cf_status cf_batch_set_text_split(cf_batch *bt, uint32_t sinks, int32_t bgzf) {
+    static_assert(CF_SPLIT_UN == kSplitUn && CF_SPLIT_AL == kSplitAl, "the public bits are the kernels'");
+    if (!bt) return CF_ERR_ARG;
+    if (sinks & ~(CF_SPLIT_UN | CF_SPLIT_AL)) { g_err = "cf_batch_set_text_split: sinks is CF_SPLIT_UN | CF_SPLIT_AL or 0"; return CF_ERR_ARG; }
+    bt->splitSinks = sinks; bt->splitBgzf = sinks && bgzf;
+    return CF_OK;
+}
+cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
+    if (!bt || !out) return CF_ERR_ARG;
+    if (bt->resultFormat != CF_RESULTS_NARROW) { g_err = "cf_batch_wait_text_split needs a slot whose result format is CF_RESULTS_NARROW"; return CF_ERR_ARG; }
+    if (!bt->fromText) { g_err = "cf_batch_wait_text_split: the slot's reads did not come as text (cf_batch_upload_text): there are no readIDs on the device"; return CF_ERR_ARG; }
+    if (!bt->splitSinks) { g_err = "cf_batch_wait_text_split: no split is set (cf_batch_set_text_split)"; return CF_ERR_ARG; }
+    if (!bt->finished || !bt->textDone) { g_err = "cf_batch_wait_text_split: the batch has not been waited for with cf_batch_wait_text / cf_batch_wait_text_bgzf"; return CF_ERR_ARG; }
+    uint32_t member = kDefMember;
+    if (bt->splitBgzf) {
+        if (const char *v = cfamd::cf_knob("CF_BGZF_OUT_MEMBER")) member = (uint32_t)std::strtoul(v, nullptr, 10);
+        if (!def_member_ok(member)) { g_err = "CF_BGZF_OUT_MEMBER: a multiple of 64, from 64 to 65280"; return CF_ERR_ARG; }
+    }
+    const cf_status rc = guard([&] {
+        cf_classifier *cl = bt->cl;
+        HIP_OK(hipSetDevice(cl->ix->device));
+        if (!bt->splitDone) {
+            hipStream_t st = bt->stream;
+            const uint64_t nq = bt->nQueries;
+            const bool bgzf = bt->splitBgzf;
+            DTextSplit d{};
+            d.text = bt->text.p; d.idOff = bt->txIdOff.p; d.idLen = bt->txIdLen.p; d.rlen = bt->rlen.p; d.qinfo = bt->qinfo.p;
+            d.woff = bt->woff.p; d.bases = bt->bases.p; d.nmask = bt->nmask.p; d.qualOff = bt->textFastq ? bt->txQualOff.p : nullptr;
+            d.nQueries = (uint32_t)nq; d.paired = (uint32_t)bt->paired; d.sinks = bt->splitSinks;
+            uint32_t mask = 0;
+            for (uint32_t s = 0; s < kSplitSinks; s++) {
+                bt->spBytes[s] = bt->spPlain[s] = bt->spRecords[s] = 0;
+                if (!((d.sinks >> (s >> 1)) & 1u) || (!d.paired && (s & 1u))) continue;      // (split_sink_on)
+                mask |= 1u << s;
+                bt->spSize[s].ensure(nq + 16); bt->spOff[s].ensure(nq + 16);
+                d.size[s] = bt->spSize[s].p; d.off[s] = bt->spOff[s].p;
+            }
+            bt->splitMs = 0;
+            if (nq) {
+                bt->spRec.ensure(kSplitSinks); bt->hSpTotal.ensure(3 * kSplitSinks);
+                bt->txTileA.ensure(scan_tiles_for(nq) + 1); bt->txTileC.ensure(scan_tiles_for(nq) + 1);
+                d.nRec = bt->spRec.p;
+                for (auto &e : bt->evSplit) if (!e) HIP_OK(hipEventCreate(&e));
+                const dim3 bl(256), gq((unsigned)((nq + 255) / 256));
+                uint64_t *const tot = bt->hSpTotal.p;
+                std::memset(tot, 0, 3 * kSplitSinks * 8);
+                HIP_OK(hipMemsetAsync(bt->spRec.p, 0, kSplitSinks * sizeof(unsigned long long), st));
+                HIP_OK(hipEventRecord(bt->evSplit[0], st));
+                hipLaunchKernelGGL(k_split_size, gq, bl, 0, st, d);
+                for (uint32_t s = 0; s < kSplitSinks; s++) {
+                    if (!(mask >> s & 1u)) continue;
+                    scan_enqueue<SCAN_PLAIN>(bt->spSize[s].p, nq, bt->spOff[s].p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
+                    HIP_OK(hipMemcpyAsync(tot + s, bt->spOff[s].p + nq, 8, hipMemcpyDeviceToHost, st));
+                }
+                HIP_OK(hipEventRecord(bt->evSplit[1], st));
+                HIP_OK(hipMemcpyAsync(tot + kSplitSinks, bt->spRec.p, kSplitSinks * 8, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipStreamSynchronize(st));
+                // the sinks' sizes are known: their room (outside the timed stretches: a buffer that grows is allocated here)
+                uint64_t nMembers[kSplitSinks] = {};
+                for (uint32_t s = 0; s < kSplitSinks; s++) {
+                    if (!(mask >> s & 1u)) continue;
+                    const uint64_t total = tot[s], nm = bgzf ? (total + member - 1) / member : 0;
+                    nMembers[s] = nm;
+                    // (BGZF: the members are moved together into the room the text lay in, as cf_batch_wait_text_bgzf's are)
+                    bt->spOut[s].ensure(std::max<uint64_t>(total + kInfPad, nm * def_stride(member)) + 8);
+                    bt->hSpOut[s].ensure((bgzf ? nm * def_stride(member) : total) + 16);
+                    if (nm) {
+                        bt->spZ[s].ensure(nm * def_stride(member)); bt->spZSize[s].ensure(nm + 16); bt->spZOff[s].ensure(nm + 16);
+                        bt->spTileA[s].ensure(scan_tiles_for(nm) + 1); bt->spTileC[s].ensure(scan_tiles_for(nm) + 1);
+                    }
+                    d.out[s] = bt->spOut[s].p; d.cap[s] = total;
+                    bt->spPlain[s] = total; bt->spRecords[s] = tot[kSplitSinks + s];
+                }
+                HIP_OK(hipEventRecord(bt->evSplit[2], st));
+                hipLaunchKernelGGL(k_split_write, gq, bl, 0, st, d);
+                HIP_OK(hipEventRecord(bt->evSplit[3], st));
+                // plain: the text comes back as it is.  BGZF: every sink's deflate, sums and compaction are queued with buffers of
+                // their own, so that the host waits once for all the sinks' sizes and then fetches the members
+                for (uint32_t s = 0; s < kSplitSinks; s++) {
+                    if (!(mask >> s & 1u)) continue;
+                    const uint64_t total = tot[s], nm = nMembers[s];
+                    if (!bgzf) { bt->spBytes[s] = total; if (total) HIP_OK(hipMemcpyAsync(bt->hSpOut[s].p, bt->spOut[s].p, total, hipMemcpyDeviceToHost, st)); continue; }
+                    if (!nm) continue;
+                    const DDeflate dd{bt->spOut[s].p, total, member, (uint32_t)nm, bt->spZ[s].p, bt->spZSize[s].p};
+                    hipLaunchKernelGGL(k_deflate, dim3((unsigned)((nm + 1) / 2)), dim3(2 * CF_WAVE), 0, st, dd);
+                    scan_enqueue<SCAN_PLAIN>(bt->spZSize[s].p, nm, bt->spZOff[s].p, nullptr, bt->spTileA[s].p, bt->spTileC[s].p, st);
+                    const DDefCompact dc{bt->spZ[s].p, def_stride(member), (uint32_t)nm, bt->spZSize[s].p, bt->spZOff[s].p, bt->spOut[s].p};
+                    hipLaunchKernelGGL(k_deflate_compact, dim3((unsigned)nm), dim3(256), 0, st, dc);
+                    HIP_OK(hipMemcpyAsync(tot + 2 * kSplitSinks + s, bt->spZOff[s].p + nm, 8, hipMemcpyDeviceToHost, st));
+                }
+                if (bgzf) {
+                    HIP_OK(hipStreamSynchronize(st));
+                    for (uint32_t s = 0; s < kSplitSinks; s++) {
+                        if (!nMembers[s]) continue;
+                        const uint64_t zb = tot[2 * kSplitSinks + s];
+                        if (zb > nMembers[s] * def_stride(member)) throw std::logic_error("the BGZF members outgrew their room");
+                        bt->spBytes[s] = zb;
+                        HIP_OK(hipMemcpyAsync(bt->hSpOut[s].p, bt->spOut[s].p, zb, hipMemcpyDeviceToHost, st));
+                    }
+                }
+                HIP_OK(hipStreamSynchronize(st));
+                HIP_OK(hipGetLastError());
+                float msA = 0, msB = 0;
+                HIP_OK(hipEventElapsedTime(&msA, bt->evSplit[0], bt->evSplit[1]));
+                HIP_OK(hipEventElapsedTime(&msB, bt->evSplit[2], bt->evSplit[3]));
+                bt->splitMs = msA + msB;
+            }
+            bt->rec.split_sinks = nq ? mask : 0u;
+            bt->splitDone = true;
+        }
+        for (uint32_t s = 0; s < kSplitSinks; s++) {
+            out->sink[s].text = bt->spBytes[s] ? reinterpret_cast<const char *>(bt->hSpOut[s].p) : "";
+            out->sink[s].n_bytes = bt->spBytes[s]; out->sink[s].plain_bytes = bt->spPlain[s]; out->sink[s].n_records = bt->spRecords[s];
+        }
+    });
+    if (rc != CF_OK) (void)hipStreamSynchronize(bt->stream);
+    return rc;
+}
+cf_status cf_batch_split_ms(const cf_batch *bt, float *ms) {
+    if (!bt || !ms) return CF_ERR_ARG;
+    *ms = bt->splitMs;
+    return CF_OK;
+}
 
 cf_status cf_batch_deflate_ms(const cf_batch *bt, float *ms) {
     if (!bt || !ms) return CF_ERR_ARG;

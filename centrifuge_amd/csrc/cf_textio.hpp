@@ -961,4 +961,78 @@ CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t 
     if (live && q + 1 == f.nQueries) f.st->outBytes = f.outOff[f.nQueries];
 }
 
+// ---- egress: the reads themselves (--un / --al / --un-conc / --al-conc: the reference's wrapper script has centrifuge-class print
+// readSeq and readQual, cuts the two columns off again and writes a FASTQ record per ROW; here the records are made from what the
+// batch holds anyway).  A sink is one file's text: 0 unclassified (mates: their first reads), 1 the unclassified pairs' second
+// reads, 2 and 3 the same for the classified.  A query writes one record per printed row — max(1, rows) copies of
+//   @readID \n bases \n + \n qualities \n
+// — into the sinks of its class; an unpaired batch feeds sinks 0 and 2 only, and a class nobody asked for is neither sized nor
+// written.  Both mates' records carry the row's readID (mate 1's); bases come from the packed words (trimmed, upper case),
+// qualities from the block (FASTA: 'I').  split_size_body, one thread per query, leaves the bytes per sink; behind the exclusive
+// sums split_write_body writes them — a record at a time by the WHOLE wavefront (fmt_wave_bytes / fmt_wave_seq: aligned dwords),
+// what a lane knows of its own query handed round by shuffles.
+enum : uint32_t { kSplitUn = 1u, kSplitAl = 2u, kSplitSinks = 4u };
+struct DTextSplit {
+    const uint8_t *text;
+    const uint32_t *idOff, *idLen, *rlen;
+    const uint8_t *qinfo;
+    const uint64_t *woff, *bases;
+    const uint32_t *nmask, *qualOff;         // qualOff nullptr: FASTA
+    uint32_t nQueries, paired, sinks;        // sinks: kSplitUn | kSplitAl
+    uint32_t *size[kSplitSinks];             // per query (a sink that is off: nullptr)
+    const uint64_t *off[kSplitSinks];        // exclusive sums of size
+    uint8_t *out[kSplitSinks];               // dword-aligned
+    uint64_t cap[kSplitSinks];
+    unsigned long long *nRec;                // [kSplitSinks]: records per sink (added to)
+};
+CF_DEV bool split_sink_on(const DTextSplit &d, uint32_t s) { return ((d.sinks >> (s >> 1)) & 1u) != 0 && (d.paired || !(s & 1u)); }
+CF_DEV void split_size_body(const DTextSplit &d, uint32_t q) {
+    const bool live = q < d.nQueries;
+    uint32_t cls = 0, copies = 0;
+    if (live) {
+        const uint32_t n = d.qinfo[q] & 0x3fu, ra = d.paired ? 2 * q : q, idn = d.idLen[ra];
+        cls = n ? 1u : 0u; copies = n ? n : 1u;
+        for (uint32_t s = 0; s < kSplitSinks; s++)
+            if (split_sink_on(d, s)) d.size[s][q] = (s >> 1) == cls ? copies * (1u + idn + 1u + d.rlen[ra + (s & 1u)] + 3u + d.rlen[ra + (s & 1u)] + 1u) : 0u;
+    }
+    // the records per class: over the wavefront first, one atomic per wavefront and sink
+    for (uint32_t c = 0; c < 2; c++) {
+        if (!split_sink_on(d, 2 * c)) continue;                          // (the same for every thread of the launch)
+        unsigned long long v = live && cls == c ? copies : 0u;
+        for (int m = CF_WAVE / 2; m > 0; m >>= 1) v += cf_shfl_xor(v, m);
+        if (cf_lane() == 0 && v) { cf_atomic_add(&d.nRec[2 * c], v); if (d.paired) cf_atomic_add(&d.nRec[2 * c + 1], v); }
+    }
+}
+// one record at dst, whose place in the sink is `at` bytes past a dword boundary: every lane of the wavefront, the same arguments
+CF_DEV void split_wave_record(const DTextSplit &d, uint8_t *dst, uint32_t at, uint32_t idOff, uint32_t idn, uint32_t r, uint32_t len, uint32_t lane) {
+    const uint64_t wo = d.woff[r];
+    const uint32_t qo = d.qualOff ? d.qualOff[r] : 0u;
+    const uint32_t pSeq = 1u + idn + 1u, pQual = pSeq + len + 3u;
+    if (lane == 0) { dst[0] = '@'; dst[pSeq - 1] = '\n'; dst[pQual + len] = '\n'; }
+    for (uint32_t i = lane; i < 3; i += CF_WAVE) dst[pSeq + len + i] = i == 1 ? (uint8_t)'+' : (uint8_t)'\n';
+    fmt_wave_bytes(dst + 1, at + 1, d.text, idOff, idn, lane);
+    fmt_wave_seq(dst + pSeq, at + pSeq, d.bases + wo, d.nmask + wo, len, lane);
+    fmt_wave_bytes(dst + pQual, at + pQual, d.qualOff ? d.text : nullptr, qo, len, lane);
+}
+CF_DEV void split_write_body(const DTextSplit &d, uint32_t q) {
+    const bool live = q < d.nQueries;
+    const uint32_t lane = cf_lane(), q0 = q - lane;
+    const uint32_t ra = d.paired ? 2 * q : q;
+    const uint32_t myId = live ? d.idLen[ra] : 0u, myIdOff = live ? d.idOff[ra] : 0u;
+    for (uint32_t s = 0; s < kSplitSinks; s++) {
+        if (!split_sink_on(d, s)) continue;                              // (the same for every thread of the launch)
+        const uint32_t mySize = live ? d.size[s][q] : 0u, myLen = live ? d.rlen[ra + (s & 1u)] : 0u;
+        const uint64_t myOff = live ? d.off[s][q] : 0;
+        uint64_t pend = cf_ballot(mySize != 0 && myOff + mySize <= d.cap[s]);
+        while (pend) {
+            const int l = cf_ctz64(pend);
+            pend &= pend - 1;
+            const uint32_t size = cf_shfl(mySize, l), len = cf_shfl(myLen, l), idn = cf_shfl(myId, l), idOff = cf_shfl(myIdOff, l);
+            const uint64_t o = cf_shfl(myOff, l);
+            const uint32_t ql = q0 + (uint32_t)l, r = (d.paired ? 2 * ql : ql) + (s & 1u), rec = 1u + idn + 1u + len + 3u + len + 1u;
+            for (uint32_t c = 0; c * rec < size; c++) split_wave_record(d, d.out[s] + o + (uint64_t)c * rec, (uint32_t)((o + (uint64_t)c * rec) & 3u), idOff, idn, r, len, lane);
+        }
+    }
+}
+
 }  // namespace cfamd

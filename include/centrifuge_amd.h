@@ -450,6 +450,38 @@ cf_status cf_batch_set_text_columns(cf_batch *, const int32_t *cols, uint32_t n_
 #define CF_TEXT_EMPTY_SEQ 32u
 cf_status cf_batch_set_text_trim(cf_batch *, uint32_t trim5, uint32_t trim3);
 cf_status cf_batch_set_text_skip(cf_batch *, uint64_t skip_reads);
+/* The reads themselves, split by what became of them (the reference's --un / --al / --un-conc / --al-conc; its wrapper script,
+ * centrifuge:212-227, 723-771, 855-931, makes them from the readSeq / readQual columns of the output's rows): for EVERY PRINTED ROW
+ * of a query — a query with n assignments prints n rows, one without prints one — the FASTQ record
+ *     @readID \n bases \n + \n qualities \n
+ * readID as the row prints it, bases the trimmed upper-case A C G T N of readSeq, qualities those of readQual (FASTA input: 'I').
+ * Unpaired reads go to sink 0 (no assignment) or 2; of mates both reads carry the row's readID and go to sinks 0 and 1 (no
+ * assignment: mate 1, mate 2) or 2 and 3.  The records of a sink stand in the order of the text's rows.
+ * cf_batch_set_text_split names the classes (CF_SPLIT_UN | CF_SPLIT_AL) the slot's batches are split into, 0 switches it off.  The
+ * setting is read by cf_batch_wait_text_split alone (nothing of the upload, the kernels or cf_batch_wait_text depends on it), so it
+ * holds for every batch whose FIRST cf_batch_wait_text_split follows the call — the batch that was just waited for included: a
+ * caller who learns a block's kind (mates or not) from the upload may set it then; bgzf != 0: each sink comes back as whole BGZF members deflated on the device (as cf_batch_wait_text_bgzf's text does).  A
+ * slot that never sets a split launches what it launched before (cf_launch_record::split_sinks stays 0).
+ * cf_batch_wait_text_split is called after the batch's cf_batch_wait_text / cf_batch_wait_text_bgzf and returns the four sinks in
+ * the slot's pinned memory (valid until the slot's next upload); a class that is off, and sinks 1 and 3 of an unpaired batch, are
+ * empty.  plain_bytes: the sink's text (= n_bytes without bgzf), n_records: its records.  A second call returns the same.
+ * CF_ERR_ARG (cf_last_error says which): the batch did not come as text, the slot's result format is not CF_RESULTS_NARROW, no
+ * split is set, or the batch has not been waited for as text. */
+#define CF_SPLIT_UN 1u
+#define CF_SPLIT_AL 2u
+typedef struct cf_split_sink {
+    const char *text;
+    uint64_t n_bytes, plain_bytes, n_records;
+} cf_split_sink;
+typedef struct cf_split_text {
+    cf_split_sink sink[4];   /* [0] un / un mate 1, [1] un mate 2, [2] al / al mate 1, [3] al mate 2 */
+} cf_split_text;
+cf_status cf_batch_set_text_split(cf_batch *, uint32_t sinks, int32_t bgzf);
+cf_status cf_batch_wait_text_split(cf_batch *, cf_split_text *out);
+/* the device time of the split's kernels in the slot's last cf_batch_wait_text_split: two stretches between HIP events, added —
+ * k_split_size with the sums per sink, and k_split_write; what lies between them (the host learns the sizes and makes room) and
+ * the deflate behind them are not in it */
+cf_status cf_batch_split_ms(const cf_batch *, float *ms);
 
 /* pinned (page-locked) host memory: what makes the transfers of the async calls truly asynchronous */
 cf_status cf_host_alloc(void **p, size_t bytes);
@@ -695,6 +727,7 @@ typedef struct cf_launch_record {
     uint32_t passes;           /* passes of the row stage */
     int32_t  pos_form;         /* the index resolves hits in their position form */
     uint32_t pos_shift;        /* ... with 2^pos_shift positions per bucket */
+    uint32_t split_sinks;      /* one bit per sink k_split_size / k_split_write were launched for (cf_batch_wait_text_split); 0: they were not */
 } cf_launch_record;
 cf_status cf_batch_debug_launch(const cf_batch *, cf_launch_record *);
 

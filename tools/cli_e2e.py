@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """End-to-end wall time of the centrifuge-class front ends (ours vs the reference binary) on one
 FASTA file: index built by the GPU builder, reads sampled from the genomes.
-usage: cli_e2e.py <genomes> <genome length> <reads> [noref | outbgzf [other centrifuge-class] | kreport [other centrifuge-class]]
-(outbgzf: our plain output against --out-bgzf, another build's plain run beside them, and gzip -1 of the TSV on 16 cores;
+usage: cli_e2e.py <genomes> <genome length> <reads> [noref | outbgzf [other centrifuge-class] | kreport [other centrifuge-class] | split [other centrifuge-class]]
+(split: --un / --al on the device text path and with --host-io, the run without them, another build's run with them beside those;
+outbgzf: our plain output against --out-bgzf, another build's plain run beside them, and gzip -1 of the TSV on 16 cores;
 kreport: our plain run against --kreport-file, another build's plain run beside them, then centrifuge-kreport on the TSV)"""
 import os
 import subprocess
@@ -94,6 +95,40 @@ def main():
         same = open(os.path.join(d, "tool.txt"), "rb").read() == open(kr, "rb").read()
         print("--kreport-file identical to centrifuge-kreport's output: %s (%d bytes); TSV identical to the plain run's: %s" % (
             same, os.path.getsize(kr), subprocess.run(["cmp", "-s", os.path.join(d, "plain.out"), os.path.join(d, "kreport.out")]).returncode == 0), flush=True)
+        return
+    if len(sys.argv) > 4 and sys.argv[4] == "split":
+        # --un / --al: another build's binary (the parent commit's, which ignores the two options) with them, this tree with them on the
+        # device text path and with --host-io, and this tree without them, three runs of each in turn: whole process, the -t lines
+        # (search wall, k_split_*'s HIP-event time per batch), the bytes of the TSV and of the two read files
+        keep = ("search wall", "Device text", "Read split")
+        un, al = os.path.join(d, "un.fq"), os.path.join(d, "al.fq")
+        opts = ["--un", un, "--al", al]
+        forms = ([("parent", sys.argv[5], opts)] if len(sys.argv) > 5 else []) + [("split", ours, opts), ("split-host-io", ours, opts + ["--host-io"]), ("plain", ours, [])]
+        for tag, exe, extra in forms * 3:
+            out = os.path.join(d, tag + ".out")
+            for f in (un, al):
+                if os.path.exists(f):
+                    os.remove(f)
+            t0 = time.time()
+            r = subprocess.run([exe, "-f", "-t", "-p", "8", "-x", os.path.join(d, "idx"), "-U", os.path.join(d, "reads.fa"), "-S", out,
+                                "--report-file", os.path.join(d, tag + ".rep")] + extra, capture_output=True, text=True, timeout=600)
+            dt = time.time() - t0
+            sizes = [os.path.getsize(f) if os.path.exists(f) else -1 for f in (un, al)]
+            print("%-13s wall %.2fs -> %.3g reads/s  rc=%d  TSV %d bytes, --un %d, --al %d bytes | %s" % (tag, dt, n / dt, r.returncode, os.path.getsize(out), sizes[0], sizes[1],
+                  " ; ".join(l for l in r.stderr.splitlines() if any(k in l for k in keep))), flush=True)
+            if r.returncode != 0:
+                print(r.stderr[-2000:], flush=True)
+                sys.exit(1)
+            if tag == "split":
+                os.replace(un, un + ".dev"); os.replace(al, al + ".dev")
+            if tag == "split-host-io":
+                same = all(subprocess.run(["cmp", "-s", f, f + ".dev"]).returncode == 0 for f in (un, al))
+                print("read files of the device path and of --host-io identical: %s; TSV identical to the parent's / the plain run's: %s" % (
+                    same, all(subprocess.run(["cmp", "-s", os.path.join(d, "split.out"), os.path.join(d, t + ".out")]).returncode == 0
+                              for t in ("parent", "plain") if os.path.exists(os.path.join(d, t + ".out")))), flush=True)
+        for f in (un, al, un + ".dev", al + ".dev"):          # (some twenty gigabytes)
+            if os.path.exists(f):
+                os.remove(f)
         return
     noref = len(sys.argv) > 4 and sys.argv[4] == "noref"
     runs = [("ours -p 8", ours, 8), ("ours -p 1", ours, 1)] + ([] if noref else [("reference -p 8", ref, 8)])
