@@ -74,6 +74,9 @@ struct Opts {
     std::vector<std::string> colNames = {"readID", "seqID", "taxID", "score", "2ndBestScore", "hitLength", "queryLength", "numMatches"};
     std::vector<int> cols;
 };
+// a debug knob (cf_knobs.hpp) that is set to a number other than 0 / that is set to 0: a knob that is not set is neither
+bool knobOn(const char *name) { const char *v = cfamd::cf_knob(name); return v && std::atoi(v); }
+bool knobOff(const char *name) { const char *v = cfamd::cf_knob(name); return v && !std::atoi(v); }
 
 // Leaves centrifuge() with a return code (and a message for stderr): the entry point is a library
 // call (centrifuge.cpp:3338-3345), so nothing below may exit() or let an exception escape.
@@ -344,7 +347,7 @@ struct Batch {
     // ... or a run of whole BGZF members of a .gz file (tOff, tLen: the compressed bytes) that are inflated on the device (classifyBgzf)
     bool tBgzf = false;
     uint64_t tMembers = 0;
-    // ... or of the two BGZF files of mates (tFd2 >= 0; classifyBgzfPair): either file's range may be empty, tLast2 is the second
+    // ... or of the two BGZF files of mates (tFd2 >= 0; classifyBgzf as well): either file's range may be empty, tLast2 is the second
     // file's end, tCum / tCum2 the text (ISIZE sums) of either file up to the run's end
     bool tLast2 = false;
     uint64_t tCum = 0, tCum2 = 0;
@@ -1005,27 +1008,112 @@ struct Runner {
         return true;
     }
 
+    int32_t textFormatCode() const {
+        return o.format == ReadFormat::Fasta ? CF_TEXT_FASTA : o.format == ReadFormat::Tab5 ? CF_TEXT_TAB5 : o.format == ReadFormat::Tab6 ? CF_TEXT_TAB6 : CF_TEXT_FASTQ;
+    }
+    // ---- what every block of the text path goes through, whatever its kind (plain text, BGZF members, one file or mates)
+    // a GPU thread's stage seconds: the time since the lap before goes to `acc`
+    struct Lap {
+        std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+        void operator()(double &acc) { const auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(t - t0).count(); t0 = t; }
+    };
+    // the thread's pinned buffer takes `need` bytes (an eighth to spare: an input's blocks are of about one size)
+    void textBuffer(GpuThread &g, uint64_t need) {
+        if (need + 64 <= g.tinCap) return;
+        if (g.tin) cf_host_free(g.tin);
+        g.tin = nullptr; g.tinCap = 0;
+        void *q = nullptr;
+        const size_t want = (size_t)(need + need / 8 + 4096);
+        CF_TRY(cf_host_alloc(&q, want));
+        g.tin = static_cast<char *>(q); g.tinCap = want;
+    }
+    // -s / -u: of the block's n records, [drop, upTo) — `take` of them — are printed; base is the ordinal of its first record, which
+    // also names reads that have no name (pat.cpp:838-842).  The block's turn in readChain ends at once, before anything is
+    // classified: the next block's ordinal is not held up.  (o.upto counts from the file's start: it includes o.skip.)  A BGZF
+    // run that is skipped behind a refused one holds no records and does not count towards -u.
+    struct Window { uint64_t base, drop, upTo, take; };
+    Window window(const Batch &b, uint64_t n, bool counts = true) {
+        const uint64_t base = readChain.enter(b.tIdx);
+        readChain.leave(n);
+        const uint64_t drop = base >= o.skip ? 0 : std::min<uint64_t>(n, o.skip - base);
+        const uint64_t upTo = base >= o.upto ? 0 : std::min<uint64_t>(n, o.upto - base);
+        if (counts && base + n >= o.upto) uptoReached = true;
+        return {base, drop, upTo, upTo > drop ? upTo - drop : 0};
+    }
+    // The block's n records (of `per` reads each) are parsed on the device and w.take > 0 of them are printed: the kernels, the rows
+    // back as text (deflated on the device under --out-bgzf), the perfect tuples into the thread's report, the Kraken-style tally's
+    // names and the --un / --al pieces.  A block that -s or -u ends in goes up once more first, those records only: again(max_reads)
+    // is the caller's upload and returns the reads it parsed (~0: the block is not in the plain form any more).
+    template <typename Again>
+    cf_results_text deviceRows(const Batch &b, GpuThread &g, Lap &lap, const Window &w, uint64_t n, uint64_t per, Again again, const char *changed, SplitPieces &pieces) {
+        if (w.take < n) {
+            CF_TRY(cf_batch_set_text_skip(g.slot, w.drop));
+            const uint64_t got = again(w.upTo < n ? w.take : 0);
+            CF_TRY(cf_batch_set_text_skip(g.slot, 0));
+            if (got != w.take * per) die(changed);
+        }
+        CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
+        lap(g.tm.create);
+        cf_results_text res{};
+        if (o.outBgzf) {
+            uint64_t plainBytes = 0;
+            float ms = 0;
+            CF_TRY(cf_batch_wait_text_bgzf(g.slot, &res, &plainBytes));
+            CF_TRY(cf_batch_deflate_ms(g.slot, &ms));
+            g.zOutText += plainBytes; g.zOutBytes += res.n_bytes; g.zOutMs += ms; g.zOutBatches++;
+        } else CF_TRY(cf_batch_wait_text(g.slot, &res));
+        lap(g.tm.classify);
+        if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
+        krDevice(b, g);
+        splitDevice(g, per == 2, pieces);
+        textBatches++; g.textBlocks++;
+        lap(g.tm.report);
+        return res;
+    }
+    // The block's text at its place in the output, behind the blocks before it (a block without text takes its turn as well).  A
+    // regular file: the turn ends before the write, so the threads write side by side, each at its own place; anything else is
+    // written in turn, and the turn ends whether the write throws or not.  The --un / --al pieces follow by their files' own chains.
+    void placeText(Batch &b, GpuThread &g, Lap &lap, const char *text, uint64_t nText, const SplitPieces &pieces) {
+        const uint64_t at = outChain.enter(b.tIdx);
+        if (outRegular) { outChain.leave(nText); if (!(outMap && copyIntoFile(text, nText, outBase + at))) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
+        else { try { writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
+        splitWriteBlock(b.tIdx, pieces);
+        lap(g.tm.write);
+        b.nq = 0;                                          // (the output stage has nothing left to do for this batch)
+    }
+    // an input starts on the text path (nothing of an earlier input is on its way: the caller drained the pipeline): the output's
+    // state, the chains, and for BGZF files the hand-over of the tails
+    void beginTextInput(bool bgzf) {
+        waitWrite();
+        std::fflush(out);
+        outFd = fileno(out);
+        struct stat sb;
+        outRegular = ::fstat(outFd, &sb) == 0 && S_ISREG(sb.st_mode);
+        outBase = outRegular ? (uint64_t)ftello(out) : 0;
+        outSize = outRegular ? (uint64_t)sb.st_size : 0;
+        outMap = !bgzf && outRegular && knobOn("CF_CLI_MAP_OUTPUT") && !o.outBgzf;
+        readChain.reset(); outChain.reset(); splitBegin(); uptoReached = false;
+        if (!bgzf) return;
+        tailChain.reset();
+        zTail.clear(); zTail2.clear(); zStopped = false; zResumeHead.clear(); zResumeHead2.clear(); zWhy.clear(); zCons = zCons2 = 0;
+    }
+    // ... and has gone through it: the output continues behind this input's text
+    void endTextInput() {
+        splitEnd();
+        const uint64_t end = outBase + outChain.sum;
+        if (outRegular && outSize > end && ::ftruncate(outFd, (off_t)end) != 0) die("error writing the classification output");
+        if (outRegular && fseeko(out, (off_t)end, SEEK_SET) != 0) die("error writing the classification output");
+    }
+
     // The device text path, one block on one GPU thread from the file to the output: the block's bytes into the thread's pinned
     // buffer, up as they are (cf_batch_upload_text: records, lengths, seeds and packed words are made on the device), the kernels,
     // and the default columns back as text (cf_batch_wait_text) — written at the block's own place in the output.  A block with a
     // record outside the plain form is parsed by the host parser instead (and its rows formatted here): same bytes out.
-    int32_t textFormatCode() const {
-        return o.format == ReadFormat::Fasta ? CF_TEXT_FASTA : o.format == ReadFormat::Tab5 ? CF_TEXT_TAB5 : o.format == ReadFormat::Tab6 ? CF_TEXT_TAB6 : CF_TEXT_FASTQ;
-    }
     void classifyText(Batch &b, GpuThread &g, size_t gi) {
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](double &acc) { const auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(t - t0).count(); t0 = t; };
+        Lap lap;
         const bool mates = b.tFd2 >= 0;
         const uint64_t at2 = (b.tLen + 4095) & ~4095ull;               // the second file's block behind the first in the same buffer
-        const uint64_t need = mates ? at2 + b.tLen2 : b.tLen;
-        if (need + 64 > g.tinCap) {
-            if (g.tin) cf_host_free(g.tin);
-            g.tin = nullptr; g.tinCap = 0;
-            void *q = nullptr;
-            const size_t want = (size_t)(need + need / 8 + 4096);
-            CF_TRY(cf_host_alloc(&q, want));
-            g.tin = static_cast<char *>(q); g.tinCap = want;
-        }
+        textBuffer(g, mates ? at2 + b.tLen2 : b.tLen);
         readFileRange(b.tFd, g.tin, (size_t)b.tLen, b.tOff, *b.tPath);
         if (mates) readFileRange(b.tFd2, g.tin + at2, (size_t)b.tLen2, b.tOff2, *b.tPath2);
         lap(g.tm.read);
@@ -1037,8 +1125,7 @@ struct Runner {
         if (mates) { in.text2 = g.tin + at2; in.n_bytes2 = b.tLen2; }
         uint64_t per = mates ? 2 : 1;
         cf_text_info info{};
-        const bool tryDevice = !(cfamd::cf_knob("CF_CLI_TEXT_HOST_PARSE") && std::atoi(cfamd::cf_knob("CF_CLI_TEXT_HOST_PARSE")));   // (the tests: every block through the fallback)
-        if (tryDevice) CF_TRY(cf_batch_upload_text(g.slot, &in, g.stream, &info)); else info.irregular = 1;
+        if (!knobOn("CF_CLI_TEXT_HOST_PARSE")) CF_TRY(cf_batch_upload_text(g.slot, &in, g.stream, &info)); else info.irregular = 1;   // (the tests: every block through the fallback)
         lap(g.tm.parse);
         bool onHost = info.irregular != 0;
         if (info.paired) per = 2;                                       // (a tabbed block of pair lines)
@@ -1078,44 +1165,20 @@ struct Runner {
             }
             lap(g.tm.hostParse);
         }
-        // the ordinal of the block's first read: -u, and the names of reads that have none (pat.cpp:838-842)
-        const uint64_t base = readChain.enter(b.tIdx);
-        readChain.leave(nReads);
-        // -s / -u: the block's records [drop, drop + take) are printed (o.upto counts from the file's start: it includes o.skip)
-        const uint64_t drop = base >= o.skip ? 0 : std::min<uint64_t>(nReads, o.skip - base);
-        const uint64_t upTo = base >= o.upto ? 0 : std::min<uint64_t>(nReads, o.upto - base);
-        const uint64_t take = upTo > drop ? upTo - drop : 0;
-        if (base + nReads >= o.upto) uptoReached = true;
+        const Window w = window(b, nReads);
+        const uint64_t base = w.base, drop = w.drop, take = w.take;
         const char *text = "";
         uint64_t nText = 0;
         SplitPieces pieces;
-        if (take == 0) { /* (past -u: nothing of this block is printed) */ }
+        if (take == 0) { /* (in front of -s or past -u: nothing of this block is printed) */ }
         else if (!onHost) {
-            if (take < nReads) {                                        // the block -s ends in or -u ends in: once more, those reads only
-                in.max_reads = upTo < nReads ? take : 0;
-                CF_TRY(cf_batch_set_text_skip(g.slot, drop));
+            auto again = [&](uint64_t maxReads) {
+                in.max_reads = maxReads;
                 CF_TRY(cf_batch_upload_text(g.slot, &in, g.stream, &info));
-                CF_TRY(cf_batch_set_text_skip(g.slot, 0));
-                if (info.irregular || info.n_reads != take * per) die("internal error: a block changed between two parses");
-            }
-            CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
-            lap(g.tm.create);
-            cf_results_text res{};
-            uint64_t plainBytes = 0;
-            if (o.outBgzf) {
-                CF_TRY(cf_batch_wait_text_bgzf(g.slot, &res, &plainBytes));
-                float ms = 0;
-                CF_TRY(cf_batch_deflate_ms(g.slot, &ms));
-                g.zOutText += plainBytes; g.zOutBytes += res.n_bytes; g.zOutMs += ms; g.zOutBatches++;
-            } else CF_TRY(cf_batch_wait_text(g.slot, &res));
-            lap(g.tm.classify);
-            if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
-            krDevice(b, g);
-            splitDevice(g, per == 2, pieces);
+                return info.irregular ? ~0ull : (uint64_t)info.n_reads;
+            };
+            const cf_results_text res = deviceRows(b, g, lap, w, nReads, per, again, "internal error: a block changed between two parses", pieces);
             text = res.text; nText = res.n_bytes;
-            b.nq = res.n_queries;
-            textBatches++; g.textBlocks++;
-            lap(g.tm.report);
         } else {
             g.hostBlocks++;
             for (auto &t : g.spText) t.clear();
@@ -1213,192 +1276,75 @@ struct Runner {
             if (o.outBgzf) { bgzfHost(text, nText, g.zText); text = g.zText.data(); nText = g.zText.size(); }
             if (splitOn) splitHostPieces(g, pieces);
         }
-        // the block's place in the output: behind the blocks before it
-        const uint64_t at = outChain.enter(b.tIdx);
-        if (outRegular) { outChain.leave(nText); if (!(outMap && copyIntoFile(text, nText, outBase + at))) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
-        else { try { writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
-        splitWriteBlock(b.tIdx, pieces);
-        lap(g.tm.write);
-        b.nq = 0;                                          // (the output stage has nothing left to do for this batch)
+        placeText(b, g, lap, text, nText, pieces);
     }
 
-    // A run of whole BGZF members on one GPU thread: the compressed bytes into the thread's pinned buffer and up as they are
-    // (cf_batch_upload_bgzf: inflated, cut behind the last whole record and parsed on the device) with the tail of the run before
-    // in front; the tail that comes back is handed on at once, and only then the kernels, the rows as text and the write follow —
-    // they overlap with the next run's upload.  A run the device refuses (a record outside the plain form, a corrupt member, a
-    // tail beyond the slot's room) ends the way for the file: the producer hands the rest to the parser pool, from this run's first member.
+    // A run of whole BGZF members on one GPU thread — of one file, or (b.tFd2 >= 0) of the two files of mates, either of whose ranges
+    // may be empty: the compressed bytes into the thread's pinned buffer and up as they are (cf_batch_upload_bgzf[_pair]: inflated,
+    // cut behind the last whole record — mates: both texts behind the same number of records, readChain counts pairs — and parsed on
+    // the device) with the tail of the run before in front; the tail that comes back is handed on at once, and only then the
+    // kernels, the rows as text and the write follow — they overlap with the next run's upload.  A run the device refuses (a record
+    // outside the plain form, a corrupt member, a tail beyond the slot's room) ends the way for the input: the producer hands the
+    // rest to the parser pool, from this run's first members.
     void classifyBgzf(Batch &b, GpuThread &g) {
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](double &acc) { const auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(t - t0).count(); t0 = t; };
-        if (b.tLen + 64 > g.tinCap) {
-            if (g.tin) cf_host_free(g.tin);
-            g.tin = nullptr; g.tinCap = 0;
-            void *q = nullptr;
-            const size_t want = (size_t)(b.tLen + b.tLen / 8 + 4096);
-            CF_TRY(cf_host_alloc(&q, want));
-            g.tin = static_cast<char *>(q); g.tinCap = want;
-        }
-        readFileRange(b.tFd, g.tin, (size_t)b.tLen, b.tOff, *b.tPath);
-        lap(g.tm.read);
-        CF_TRY(cf_batch_set_result_format(g.slot, CF_RESULTS_NARROW));
-        cf_bgzf_reads in{};
-        in.members = g.tin; in.n_bytes = b.tLen; in.format = textFormatCode();
-        in.global_seed = o.seed; in.max_reads = 0; in.last = b.tLast ? 1 : 0;
-        cf_text_info info{};
-        cf_bgzf_info zi{};
-        (void)tailChain.enter(b.tIdx);
-        bool skip = zStopped;
-        if (!skip) {
-            g.zHead = zTail;
-            in.head = g.zHead.data(); in.head_bytes = g.zHead.size();
-            const cf_status st = cf_batch_upload_bgzf(g.slot, &in, g.stream, &info, &zi);
-            // (a text beyond the batch's 32-bit places is refused before anything is uploaded: the host path has no such limit)
-            if (st != CF_OK && st != CF_ERR_ARG) { tailChain.fail(); die(std::string("centrifuge-class: ") + cf_strerror(st) + ": " + cf_last_error()); }
-            if (st != CF_OK || info.irregular || zi.corrupt) {
-                zStopped = true; zResumeOff = b.tOff; zResumeHead = g.zHead;
-                zWhy = zi.corrupt ? "a corrupt member" : st != CF_OK ? "a run beyond the batch's size" : "a record outside the plain form";
-                skip = true;
-            } else zTail.assign(zi.tail, (size_t)zi.tail_bytes);
-        }
-        tailChain.leave(0);
-        lap(g.tm.parse);
-        const uint64_t per = info.paired ? 2 : 1;                       // (a tabbed run of pair lines: -s / -u count records)
-        const uint64_t nReads = skip ? 0 : info.n_reads / per;
-        const uint64_t base = readChain.enter(b.tIdx);
-        readChain.leave(nReads);
-        const uint64_t drop = base >= o.skip ? 0 : std::min<uint64_t>(nReads, o.skip - base);     // (-s / -u: as in classifyText)
-        const uint64_t upTo = base >= o.upto ? 0 : std::min<uint64_t>(nReads, o.upto - base);
-        const uint64_t take = upTo > drop ? upTo - drop : 0;
-        if (!skip && base + nReads >= o.upto) uptoReached = true;
-        const char *text = "";
-        uint64_t nText = 0;
-        SplitPieces pieces;
-        if (take) {
-            if (take < nReads) {                                        // the run -s ends in or -u ends in: once more, those reads only
-                in.max_reads = upTo < nReads ? take : 0;
-                CF_TRY(cf_batch_set_text_skip(g.slot, drop));
-                CF_TRY(cf_batch_upload_bgzf(g.slot, &in, g.stream, &info, &zi));
-                CF_TRY(cf_batch_set_text_skip(g.slot, 0));
-                if (info.irregular || zi.corrupt || info.n_reads != take * per) die("internal error: a run of members changed between two uploads");
-            }
-            CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
-            lap(g.tm.create);
-            cf_results_text res{};
-            uint64_t plainBytes = 0;
-            if (o.outBgzf) {
-                CF_TRY(cf_batch_wait_text_bgzf(g.slot, &res, &plainBytes));
-                float ms = 0;
-                CF_TRY(cf_batch_deflate_ms(g.slot, &ms));
-                g.zOutText += plainBytes; g.zOutBytes += res.n_bytes; g.zOutMs += ms; g.zOutBatches++;
-            } else CF_TRY(cf_batch_wait_text(g.slot, &res));
-            lap(g.tm.classify);
-            if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
-            krDevice(b, g);
-            splitDevice(g, info.paired != 0, pieces);
-            text = res.text; nText = res.n_bytes;
-            textBatches++; g.textBlocks++;
-            lap(g.tm.report);
-        }
-        if (!skip) g.zMembers += b.tMembers;
-        const uint64_t at = outChain.enter(b.tIdx);
-        if (outRegular) { outChain.leave(nText); if (nText) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
-        else { try { if (nText) writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
-        splitWriteBlock(b.tIdx, pieces);
-        lap(g.tm.write);
-        b.nq = 0;
-    }
-
-    // A run of whole BGZF members of the two files of mates on one GPU thread: classifyBgzf for two files.  Both byte ranges go into
-    // the thread's pinned buffer and up as they are (cf_batch_upload_bgzf_pair: inflated by one launch, both texts cut behind the same
-    // number of whole records) with the two tails of the run before in front; both tails that come back are handed on at once.
-    // readChain counts pairs.  A run the device refuses ends the way for both files.
-    void classifyBgzfPair(Batch &b, GpuThread &g) {
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](double &acc) { const auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(t - t0).count(); t0 = t; };
-        const uint64_t at2 = (b.tLen + 4095) & ~4095ull, need = at2 + b.tLen2;
-        if (need + 64 > g.tinCap) {
-            if (g.tin) cf_host_free(g.tin);
-            g.tin = nullptr; g.tinCap = 0;
-            void *q = nullptr;
-            const size_t want = (size_t)(need + need / 8 + 4096);
-            CF_TRY(cf_host_alloc(&q, want));
-            g.tin = static_cast<char *>(q); g.tinCap = want;
-        }
+        Lap lap;
+        const bool mates = b.tFd2 >= 0;
+        const uint64_t at2 = (b.tLen + 4095) & ~4095ull;               // the second file's members behind the first's in the same buffer
+        textBuffer(g, mates ? at2 + b.tLen2 : b.tLen);
         if (b.tLen) readFileRange(b.tFd, g.tin, (size_t)b.tLen, b.tOff, *b.tPath);
-        if (b.tLen2) readFileRange(b.tFd2, g.tin + at2, (size_t)b.tLen2, b.tOff2, *b.tPath2);
+        if (mates && b.tLen2) readFileRange(b.tFd2, g.tin + at2, (size_t)b.tLen2, b.tOff2, *b.tPath2);
         lap(g.tm.read);
         CF_TRY(cf_batch_set_result_format(g.slot, CF_RESULTS_NARROW));
         cf_bgzf_reads in1{}, in2{};
-        in1.members = g.tin; in1.n_bytes = b.tLen; in1.format = o.format == ReadFormat::Fasta ? CF_TEXT_FASTA : CF_TEXT_FASTQ;
-        in1.global_seed = o.seed; in1.max_reads = 0; in1.last = b.tLast ? 1 : 0;
+        in1.members = g.tin; in1.n_bytes = b.tLen; in1.last = b.tLast ? 1 : 0;
+        in1.format = textFormatCode();                                  // (one file: a tabbed one goes this way too; mates are FASTA or FASTQ: no tabbed run sends them here)
+        in1.global_seed = o.seed;
         in2 = in1;
         in2.members = g.tin + at2; in2.n_bytes = b.tLen2; in2.last = b.tLast2 ? 1 : 0;
         cf_text_info info{};
         cf_bgzf_info z1{}, z2{};
+        auto upload = [&](uint64_t maxReads) {
+            in1.max_reads = in2.max_reads = maxReads;
+            return mates ? cf_batch_upload_bgzf_pair(g.slot, &in1, &in2, g.stream, &info, &z1, &z2) : cf_batch_upload_bgzf(g.slot, &in1, g.stream, &info, &z1);
+        };
         (void)tailChain.enter(b.tIdx);
         bool skip = zStopped;
         if (!skip) {
             g.zHead = zTail; g.zHead2 = zTail2;
             in1.head = g.zHead.data(); in1.head_bytes = g.zHead.size();
             in2.head = g.zHead2.data(); in2.head_bytes = g.zHead2.size();
-            const cf_status st = cf_batch_upload_bgzf_pair(g.slot, &in1, &in2, g.stream, &info, &z1, &z2);
-            // (texts beyond the batch's 32-bit places are refused before anything is uploaded: the host path has no such limit)
+            const cf_status st = upload(0);
+            // (a text beyond the batch's 32-bit places is refused before anything is uploaded: the host path has no such limit)
             if (st != CF_OK && st != CF_ERR_ARG) { tailChain.fail(); die(std::string("centrifuge-class: ") + cf_strerror(st) + ": " + cf_last_error()); }
             if (st != CF_OK || info.irregular || z1.corrupt || z2.corrupt) {
                 zStopped = true; zResumeOff = b.tOff; zResumeOff2 = b.tOff2; zResumeHead = g.zHead; zResumeHead2 = g.zHead2;
                 zWhy = (z1.corrupt || z2.corrupt) ? "a corrupt member" : st != CF_OK ? "a run beyond the batch's size" : "a record outside the plain form";
                 skip = true;
             } else {
-                zTail.assign(z1.tail, (size_t)z1.tail_bytes); zTail2.assign(z2.tail, (size_t)z2.tail_bytes);
-                std::lock_guard<std::mutex> lk(tailChain.mu);            // (the producer reads the two together)
-                zCons = b.tCum - z1.tail_bytes; zCons2 = b.tCum2 - z2.tail_bytes;
+                zTail.assign(z1.tail, (size_t)z1.tail_bytes);
+                if (mates) {
+                    zTail2.assign(z2.tail, (size_t)z2.tail_bytes);
+                    std::lock_guard<std::mutex> lk(tailChain.mu);        // (the producer reads the two together)
+                    zCons = b.tCum - z1.tail_bytes; zCons2 = b.tCum2 - z2.tail_bytes;
+                }
             }
         }
         tailChain.leave(0);
         lap(g.tm.parse);
-        const uint64_t nPairs = skip ? 0 : info.n_reads / 2;
-        const uint64_t base = readChain.enter(b.tIdx);
-        readChain.leave(nPairs);
-        const uint64_t drop = base >= o.skip ? 0 : std::min<uint64_t>(nPairs, o.skip - base);     // (-s / -u: as in classifyText)
-        const uint64_t upTo = base >= o.upto ? 0 : std::min<uint64_t>(nPairs, o.upto - base);
-        const uint64_t take = upTo > drop ? upTo - drop : 0;
-        if (!skip && base + nPairs >= o.upto) uptoReached = true;
-        const char *text = "";
-        uint64_t nText = 0;
+        const uint64_t per = mates || info.paired ? 2 : 1;              // (a tabbed run of pair lines: -s / -u count records)
+        const uint64_t n = skip ? 0 : info.n_reads / per;
+        const Window w = window(b, n, !skip);
+        cf_results_text res{};
         SplitPieces pieces;
-        if (take) {
-            if (take < nPairs) {                                        // the run -s ends in or -u ends in: once more, those pairs only
-                in1.max_reads = in2.max_reads = upTo < nPairs ? take : 0;
-                CF_TRY(cf_batch_set_text_skip(g.slot, drop));
-                CF_TRY(cf_batch_upload_bgzf_pair(g.slot, &in1, &in2, g.stream, &info, &z1, &z2));
-                CF_TRY(cf_batch_set_text_skip(g.slot, 0));
-                if (info.irregular || z1.corrupt || z2.corrupt || info.n_reads != 2 * take) die("internal error: a run of members changed between two uploads");
-            }
-            CF_TRY(cf_classify_async(g.dev->clf, g.slot, g.stream));
-            lap(g.tm.create);
-            cf_results_text res{};
-            uint64_t plainBytes = 0;
-            if (o.outBgzf) {
-                CF_TRY(cf_batch_wait_text_bgzf(g.slot, &res, &plainBytes));
-                float ms = 0;
-                CF_TRY(cf_batch_deflate_ms(g.slot, &ms));
-                g.zOutText += plainBytes; g.zOutBytes += res.n_bytes; g.zOutMs += ms; g.zOutBatches++;
-            } else CF_TRY(cf_batch_wait_text(g.slot, &res));
-            lap(g.tm.classify);
-            if (g.rep && res.n_tuple_words) CF_TRY(cf_report_add_tuples(g.rep, res.tuples, res.n_tuple_words));
-            krDevice(b, g);
-            splitDevice(g, true, pieces);
-            text = res.text; nText = res.n_bytes;
-            textBatches++; g.textBlocks++;
-            lap(g.tm.report);
+        if (w.take) {
+            auto again = [&](uint64_t maxReads) {
+                CF_TRY(upload(maxReads));
+                return info.irregular || z1.corrupt || z2.corrupt ? ~0ull : (uint64_t)info.n_reads;
+            };
+            res = deviceRows(b, g, lap, w, n, per, again, "internal error: a run of members changed between two uploads", pieces);
         }
         if (!skip) g.zMembers += b.tMembers;
-        const uint64_t at = outChain.enter(b.tIdx);
-        if (outRegular) { outChain.leave(nText); if (nText) writeAll(outFd, text, (size_t)nText, true, outBase + at); }
-        else { try { if (nText) writeAll(outFd, text, (size_t)nText, false, 0); } catch (...) { outChain.leave(nText); throw; } outChain.leave(nText); }
-        splitWriteBlock(b.tIdx, pieces);
-        lap(g.tm.write);
-        b.nq = 0;
+        placeText(b, g, lap, res.text, res.n_bytes, pieces);
     }
 
     // the report file with its stderr lines (centrifuge.cpp:3134-3141,3231-3319; aln_sink.h:471-472)
@@ -1661,8 +1607,7 @@ int run(int argc, const char **argv) {
         // -5 / -3 as the record pass's window (cf_batch_set_text_trim), -s / -u by the block (cf_batch_set_text_skip, max_reads), up to CF_TEXT_MAX_COLS columns (cf_batch_set_text_columns), -k <= 63 (the narrow rows' six bits).  Every GPU thread
         // then also reads its blocks and writes its text, so there are more of them (each with a slot on the device).
         R.textCapable = !ordered && o.cols.size() <= CF_TEXT_MAX_COLS && (o.format == ReadFormat::Fasta || o.format == ReadFormat::Fastq || o.format == ReadFormat::Tab5 || o.format == ReadFormat::Tab6) &&
-                        o.khits <= 63 && !o.hostIo &&
-                        !(cfamd::cf_knob("CF_CLI_DEVICE_TEXT") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_TEXT")));
+                        o.khits <= 63 && !o.hostIo && !knobOff("CF_CLI_DEVICE_TEXT");
         const int slots = ordered ? 1 : (R.textCapable && !o.slotsSet) ? std::max(2, std::min(6, o.threads / 2)) : o.slots;
         R.gts.resize(R.devs.size() * (size_t)slots);
         for (size_t t = 0; t < R.gts.size(); t++) {
@@ -1726,7 +1671,7 @@ int run(int argc, const char **argv) {
                     queue.pop_front();
                 }
                 cv.notify_all();
-                if (b->endOfInput < 0) { if (b->isText && b->tBgzf && b->tFd2 >= 0) R.classifyBgzfPair(*b, g); else if (b->isText && b->tBgzf) R.classifyBgzf(*b, g); else if (b->isText) R.classifyText(*b, g, wi); else R.classify(*b, g); }
+                if (b->endOfInput < 0) { if (!b->isText) R.classify(*b, g); else if (b->tBgzf) R.classifyBgzf(*b, g); else R.classifyText(*b, g, wi); }
                 {
                     std::lock_guard<std::mutex> lk(mu);
                     const uint64_t sq = b->seq;
@@ -1775,6 +1720,26 @@ int run(int argc, const char **argv) {
         cv.notify_all();
         return true;
     };
+    // ... a block of the text path, timed: what the producer took to cut it, and what it waited for the pipeline
+    auto submitTimed = [&](std::unique_ptr<Batch> b, std::chrono::steady_clock::time_point tp0) -> bool {
+        const auto tp1 = std::chrono::steady_clock::now();
+        R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
+        if (!submit(std::move(b))) return false;
+        R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+        return true;
+    };
+    // the batch such a block travels in: a printed one when there is one to spare, one file's plain text until the producer says otherwise
+    auto textBatch = [&](bool paired) {
+        std::unique_ptr<Batch> b;
+        { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
+        if (!b) b = std::make_unique<Batch>();
+        b->nq = 0; b->endOfInput = -1; b->paired = paired; b->narrowRows = false; b->isText = true;
+        b->tBgzf = false; b->tMembers = 0; b->tCum = b->tCum2 = 0;
+        b->tFd2 = -1; b->tOff2 = b->tLen2 = 0; b->tPath2 = nullptr; b->tLast2 = false;
+        return b;
+    };
+    // bytes of a block: CF_TEXT_BLOCK, or the input kind's default
+    auto textBlock = [](size_t bytes) { const char *v = cfamd::cf_knob("CF_TEXT_BLOCK"); return v ? std::max<size_t>(4096, std::strtoull(v, nullptr, 10)) : bytes; };
     // every batch submitted so far is printed (false: the run is failing)
     auto drain = [&]() -> bool {
         std::unique_lock<std::mutex> lk(mu);
@@ -1804,16 +1769,8 @@ int run(int argc, const char **argv) {
             int fd1 = -1, fd2 = -1; uint64_t fs1 = 0, fs2 = 0;
             if (src1.regularFile(fd1, fs1) && src2.regularFile(fd2, fs2) && fs1 && fs2) {
                 if (!drain()) { aborted = true; break; }
-                R.waitWrite();
-                std::fflush(R.out);
-                R.outFd = fileno(R.out);
-                struct stat sb;
-                R.outRegular = ::fstat(R.outFd, &sb) == 0 && S_ISREG(sb.st_mode);
-                R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
-                R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
-                R.outMap = R.outRegular && cfamd::cf_knob("CF_CLI_MAP_OUTPUT") && std::atoi(cfamd::cf_knob("CF_CLI_MAP_OUTPUT")) && !o.outBgzf;
-                R.readChain.reset(); R.outChain.reset(); R.splitBegin(); R.uptoReached = false;
-                const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(32u << 20);
+                R.beginTextInput(false);
+                const size_t kBlock = textBlock((size_t)32u << 20);
                 void *m1 = ::mmap(nullptr, (size_t)fs1, PROT_READ, MAP_SHARED, fd1, 0), *m2 = ::mmap(nullptr, (size_t)fs2, PROT_READ, MAP_SHARED, fd2, 0);
                 struct Unmap { void *a, *b; size_t na, nb; ~Unmap() { if (a != MAP_FAILED) ::munmap(a, na); if (b != MAP_FAILED) ::munmap(b, nb); } } unmap{m1, m2, (size_t)fs1, (size_t)fs2};
                 bool changeOver = m1 == MAP_FAILED || m2 == MAP_FAILED;
@@ -1853,27 +1810,19 @@ int run(int argc, const char **argv) {
                         if (!shape || p2[ls[0]] != '@' || p2[ls[2]] != '+' || ls[2] - ls[1] != ls[4] - ls[3]) { changeOver = true; break; }
                     }
                     if ((cut1 == fs1) != (end2 == fs2)) { changeOver = true; break; }      // one file goes on where the other ends
-                    std::unique_ptr<Batch> b;
-                    { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
-                    if (!b) b = std::make_unique<Batch>();
-                    b->nq = 0; b->endOfInput = -1; b->paired = true; b->narrowRows = false;
-                    b->isText = true; b->tFd = fd1; b->tOff = pos1; b->tLen = cut1 - pos1; b->tFirst = pos1 == 0; b->tLast = cut1 == fs1; b->tIdx = idx++; b->tPath = &in.f1;
-                    b->tFd2 = fd2; b->tOff2 = pos2; b->tLen2 = end2 - pos2; b->tPath2 = &in.f2; b->tBgzf = false;
+                    std::unique_ptr<Batch> b = textBatch(true);
+                    b->tFd = fd1; b->tOff = pos1; b->tLen = cut1 - pos1; b->tFirst = pos1 == 0; b->tLast = cut1 == fs1; b->tIdx = idx++; b->tPath = &in.f1;
+                    b->tFd2 = fd2; b->tOff2 = pos2; b->tLen2 = end2 - pos2; b->tPath2 = &in.f2;
                     pos1 = cut1; pos2 = end2; pairs += n;
-                    const auto tp1 = std::chrono::steady_clock::now();
-                    R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
-                    if (!submit(std::move(b))) { aborted = true; break; }
-                    R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+                    if (!submitTimed(std::move(b), tp0)) { aborted = true; break; }
                 }
                 if (aborted || !drain()) { aborted = true; break; }
-                R.splitEnd();
-                if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
-                if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
+                R.endTextInput();
                 if (!changeOver || R.uptoReached) continue;
                 resume1 = pos1; resume2 = pos2; resumeId = pairs;     // the parser pool goes on from here
             }
             int zfd1 = -1, zfd2 = -1; uint64_t zs1 = 0, zs2 = 0;
-            const bool devInflateAll = o.devInflate == 2 && !(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE")));
+            const bool devInflateAll = o.devInflate == 2 && !knobOff("CF_CLI_DEVICE_INFLATE");
             if (devInflateAll && src1.bgzfFile(zfd1, zs1) && src2.bgzfFile(zfd2, zs2) && zs1 && zs2) {
                 // Two BGZF files of mates (--device-inflate all): the members of both are hopped here by their headers and dealt out
                 // as runs — some whole members of the first file and some of the second, CF_TEXT_BLOCK bytes of compressed plus
@@ -1883,17 +1832,8 @@ int run(int argc, const char **argv) {
                 // sampled from the files' first members at first, then what whole pairs have in fact used up — so the tails stay
                 // a member's size whatever the two files' records look like.  The first runs are small: a poor sample costs little.
                 if (!drain()) { aborted = true; break; }
-                R.waitWrite();
-                std::fflush(R.out);
-                R.outFd = fileno(R.out);
-                struct stat sb;
-                R.outRegular = ::fstat(R.outFd, &sb) == 0 && S_ISREG(sb.st_mode);
-                R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
-                R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
-                R.outMap = false;
-                R.readChain.reset(); R.outChain.reset(); R.splitBegin(); R.tailChain.reset(); R.uptoReached = false;
-                R.zTail.clear(); R.zTail2.clear(); R.zStopped = false; R.zResumeHead.clear(); R.zResumeHead2.clear(); R.zWhy.clear(); R.zCons = R.zCons2 = 0;
-                const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
+                R.beginTextInput(true);
+                const size_t kBlock = textBlock((size_t)64u << 20);
                 void *zm1 = ::mmap(nullptr, (size_t)zs1, PROT_READ, MAP_SHARED, zfd1, 0);
                 if (zm1 == MAP_FAILED) die("Error: could not map \"" + in.f1 + "\"");
                 void *zm2 = ::mmap(nullptr, (size_t)zs2, PROT_READ, MAP_SHARED, zfd2, 0);
@@ -1925,24 +1865,16 @@ int run(int argc, const char **argv) {
                     }
                     if (!nMem) break;
                     budget = std::min<size_t>(kBlock, budget * 2);
-                    std::unique_ptr<Batch> b;
-                    { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
-                    if (!b) b = std::make_unique<Batch>();
-                    b->nq = 0; b->endOfInput = -1; b->paired = true; b->narrowRows = false;
-                    b->isText = true; b->tBgzf = true; b->tMembers = nMem; b->tIdx = idx++; b->tFirst = pos[0] == 0 && pos[1] == 0;
+                    std::unique_ptr<Batch> b = textBatch(true);
+                    b->tBgzf = true; b->tMembers = nMem; b->tIdx = idx++; b->tFirst = pos[0] == 0 && pos[1] == 0;
                     b->tFd = zfd1; b->tOff = pos[0]; b->tLen = end[0] - pos[0]; b->tLast = end[0] == zs1; b->tPath = &in.f1; b->tCum = cum[0];
                     b->tFd2 = zfd2; b->tOff2 = pos[1]; b->tLen2 = end[1] - pos[1]; b->tLast2 = end[1] == zs2; b->tPath2 = &in.f2; b->tCum2 = cum[1];
                     pos[0] = end[0]; pos[1] = end[1];
-                    const auto tp1 = std::chrono::steady_clock::now();
-                    R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
-                    if (!submit(std::move(b))) { aborted = true; break; }
-                    R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+                    if (!submitTimed(std::move(b), tp0)) { aborted = true; break; }
                     { std::lock_guard<std::mutex> lk(R.tailChain.mu); if (R.zStopped) break; }       // (no run behind a refused one is of use)
                 }
                 if (aborted || !drain()) { aborted = true; break; }
-                R.splitEnd();
-                if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
-                if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
+                R.endTextInput();
                 if (R.uptoReached || (!R.zStopped && pos[0] >= zs1 && pos[1] >= zs2)) continue;
                 // the parser pool goes on with both files: from the refused run's first members with that run's heads in front, or from the bytes that are no member
                 resume1 = R.zStopped ? R.zResumeOff : pos[0]; resume2 = R.zStopped ? R.zResumeOff2 : pos[1];
@@ -1960,56 +1892,29 @@ int run(int argc, const char **argv) {
             int fd = -1; uint64_t fsize = 0;
             if (src.regularFile(fd, fsize)) {
                 if (!drain()) { aborted = true; break; }          // nothing of an earlier input is still on its way
-                R.waitWrite();
-                std::fflush(R.out);
-                R.outFd = fileno(R.out);
-                struct stat sb;
-                R.outRegular = ::fstat(R.outFd, &sb) == 0 && S_ISREG(sb.st_mode);
-                R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
-                R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
-                R.outMap = R.outRegular && cfamd::cf_knob("CF_CLI_MAP_OUTPUT") && std::atoi(cfamd::cf_knob("CF_CLI_MAP_OUTPUT")) && !o.outBgzf;
-                R.readChain.reset(); R.outChain.reset(); R.splitBegin(); R.uptoReached = false;
-                const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
+                R.beginTextInput(false);
+                const size_t kBlock = textBlock((size_t)64u << 20);
                 uint64_t pos = 0, idx = 0;
                 while (pos < fsize && !R.uptoReached) {
                     const auto tp0 = std::chrono::steady_clock::now();
                     const uint64_t cut = nextRecordCut(fd, pos, fsize, kBlock, o.format == ReadFormat::Fasta, in.f1, tabRun);
-                    std::unique_ptr<Batch> b;
-                    { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
-                    if (!b) b = std::make_unique<Batch>();
-                    b->nq = 0; b->endOfInput = -1; b->paired = false; b->narrowRows = false;
-                    b->isText = true; b->tFd = fd; b->tOff = pos; b->tLen = cut - pos; b->tFirst = pos == 0; b->tLast = cut == fsize; b->tIdx = idx++; b->tPath = &in.f1;
-                    b->tFd2 = -1; b->tLen2 = 0; b->tBgzf = false;
+                    std::unique_ptr<Batch> b = textBatch(false);
+                    b->tFd = fd; b->tOff = pos; b->tLen = cut - pos; b->tFirst = pos == 0; b->tLast = cut == fsize; b->tIdx = idx++; b->tPath = &in.f1;
                     pos = cut;
-                    const auto tp1 = std::chrono::steady_clock::now();
-                    R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
-                    if (!submit(std::move(b))) { aborted = true; break; }
-                    R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+                    if (!submitTimed(std::move(b), tp0)) { aborted = true; break; }
                 }
                 if (aborted || !drain()) { aborted = true; break; }
-                // the output continues behind this input's text
-                R.splitEnd();
-                if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
-                if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
+                R.endTextInput();
                 continue;
             }
-            const bool devInflate = o.devInflate != 0 && !(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE") && !std::atoi(cfamd::cf_knob("CF_CLI_DEVICE_INFLATE")));
+            const bool devInflate = o.devInflate != 0 && !knobOff("CF_CLI_DEVICE_INFLATE");
             if (devInflate && src.bgzfFile(fd, fsize) && fsize) {
                 // A BGZF file: its members are hopped here by their headers (BgzfImpl::fill's test) and dealt out as runs of whole
                 // members, CF_TEXT_BLOCK bytes of compressed plus inflated size at most; the GPU threads have them inflated on the
                 // device.  Where a header is not BGZF's, or at the first run the device refuses, the parser pool takes the rest.
                 if (!drain()) { aborted = true; break; }
-                R.waitWrite();
-                std::fflush(R.out);
-                R.outFd = fileno(R.out);
-                struct stat sb;
-                R.outRegular = ::fstat(R.outFd, &sb) == 0 && S_ISREG(sb.st_mode);
-                R.outBase = R.outRegular ? (uint64_t)ftello(R.out) : 0;
-                R.outSize = R.outRegular ? (uint64_t)sb.st_size : 0;
-                R.outMap = false;
-                R.readChain.reset(); R.outChain.reset(); R.splitBegin(); R.tailChain.reset(); R.uptoReached = false;
-                R.zTail.clear(); R.zStopped = false; R.zResumeHead.clear(); R.zWhy.clear();
-                const size_t kBlock = cfamd::cf_knob("CF_TEXT_BLOCK") ? std::max<size_t>(4096, std::strtoull(cfamd::cf_knob("CF_TEXT_BLOCK"), nullptr, 10)) : (size_t)(64u << 20);
+                R.beginTextInput(true);
+                const size_t kBlock = textBlock((size_t)64u << 20);
                 void *zm = ::mmap(nullptr, (size_t)fsize, PROT_READ, MAP_SHARED, fd, 0);
                 if (zm == MAP_FAILED) die("Error: could not map \"" + in.f1 + "\"");
                 struct Unmap { void *a; size_t n; ~Unmap() { ::munmap(a, n); } } unmap{zm, (size_t)fsize};
@@ -2026,23 +1931,14 @@ int run(int argc, const char **argv) {
                         bytes += bs + is; end += bs; nMem++;
                     }
                     if (!nMem) break;
-                    std::unique_ptr<Batch> b;
-                    { std::lock_guard<std::mutex> lk(mu); if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); } }
-                    if (!b) b = std::make_unique<Batch>();
-                    b->nq = 0; b->endOfInput = -1; b->paired = false; b->narrowRows = false;
-                    b->isText = true; b->tBgzf = true; b->tMembers = nMem; b->tFd = fd; b->tOff = pos; b->tLen = end - pos; b->tFirst = pos == 0; b->tLast = end == fsize; b->tIdx = idx++; b->tPath = &in.f1;
-                    b->tFd2 = -1; b->tLen2 = 0;
+                    std::unique_ptr<Batch> b = textBatch(false);
+                    b->tBgzf = true; b->tMembers = nMem; b->tFd = fd; b->tOff = pos; b->tLen = end - pos; b->tFirst = pos == 0; b->tLast = end == fsize; b->tIdx = idx++; b->tPath = &in.f1;
                     pos = end;
-                    const auto tp1 = std::chrono::steady_clock::now();
-                    R.tm.produce += std::chrono::duration<double>(tp1 - tp0).count();
-                    if (!submit(std::move(b))) { aborted = true; break; }
-                    R.tm.wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
+                    if (!submitTimed(std::move(b), tp0)) { aborted = true; break; }
                     { std::lock_guard<std::mutex> lk(R.tailChain.mu); if (R.zStopped) break; }       // (no run behind a refused one is of use)
                 }
                 if (aborted || !drain()) { aborted = true; break; }
-                R.splitEnd();
-                if (R.outRegular && R.outSize > R.outBase + R.outChain.sum && ::ftruncate(R.outFd, (off_t)(R.outBase + R.outChain.sum)) != 0) die("error writing the classification output");
-                if (R.outRegular && fseeko(R.out, (off_t)(R.outBase + R.outChain.sum), SEEK_SET) != 0) die("error writing the classification output");
+                R.endTextInput();
                 if (R.uptoReached || (!R.zStopped && pos >= fsize)) continue;
                 // the parser pool goes on: from the refused run's first member with that run's head in front, or from the bytes that are no member
                 resume1 = R.zStopped ? R.zResumeOff : pos;
@@ -2056,8 +1952,8 @@ int run(int argc, const char **argv) {
         // interleaved into the batch pair by pair, their packed words along with their bytes (every read starts on a word).
         // A batch put together record by record (-s / -u windows, unnamed reads) goes up as bytes.  (CF_CLI_PACKED=0: bytes always; with --dump-reads
         // the knob CF_DUMP_FROM_PACKED=1 prints the bases back out of the packed form — the tests' window on it.)
-        const bool dumpPacked = o.dumpReads && cfamd::cf_knob("CF_DUMP_FROM_PACKED") && std::atoi(cfamd::cf_knob("CF_DUMP_FROM_PACKED"));
-        const bool wantPacked = o.dumpReads ? dumpPacked : !(cfamd::cf_knob("CF_CLI_PACKED") && !std::atoi(cfamd::cf_knob("CF_CLI_PACKED")));
+        const bool dumpPacked = o.dumpReads && knobOn("CF_DUMP_FROM_PACKED");
+        const bool wantPacked = o.dumpReads ? dumpPacked : !knobOff("CF_CLI_PACKED");
         const bool tabFmt = o.format == ReadFormat::Tab5 || o.format == ReadFormat::Tab6;
         ChunkedReader s1({in.f1}, o.format, o.trim5, o.trim3, o.seed, o.threads, wantPacked && !in.tab, resume1, resumeHead, in.tab);
         std::unique_ptr<ChunkedReader> s2;

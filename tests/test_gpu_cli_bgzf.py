@@ -84,6 +84,27 @@ def test_bgzf_files_are_inflated_on_the_device_and_print_the_golden_output(name,
         assert a[:2] == b[:2] and members(a[2]) == (n_members, 0) and members(b[2]) is None
 
 
+def n_reads(tsv):
+    """the reads a TSV holds rows for (a read's rows are adjacent)"""
+    ids = [ln.split(b"\t", 1)[0] for ln in tsv.split(b"\n")[1:-1]]
+    return sum(1 for i, r in enumerate(ids) if i == 0 or r != ids[i - 1])
+
+
+@pytest.mark.parametrize("window,printed", [(["-s", "13", "-u", "40"], 40), (["-s", "101"], 199)])
+def test_skip_and_upto_windows_on_a_bgzf_file_print_what_the_host_threads_print(window, printed):
+    """-s beyond the first run's records (a run of 4096 bytes holds about seven of the 300): runs of which nothing is printed, then a
+    run that starts in its middle — and, with -u, one that ends in its middle"""
+    d, _ = common.golden("synth_small")
+    with tempfile.TemporaryDirectory() as t:
+        gz = write_bgzf(os.path.join(t, "reads.fq.gz"), open(os.path.join(d, "reads.fq"), "rb").read())
+        args = ["-q", "-t", "-p", "4", "-x", os.path.join(d, "idx"), "-U", gz] + window
+        a = run(args, t, env={"CF_TEXT_BLOCK": "4096"}, tag="a")
+        b = run(args + ["--host-io"], t, tag="b")
+        assert a[0] == b[0], common.first_diff(a[0].decode("latin1"), b[0].decode("latin1"))
+        assert a[1] == b[1] and n_reads(b[0]) == printed
+        assert members(a[2])[0] >= 3 and members(a[2])[1] == 0 and members(b[2]) is None, a[2]
+
+
 def test_the_switches_leave_bgzf_files_to_the_host_threads():
     d, cases = common.golden("synth_small")
     c = [x for x in cases if x["name"] == "fastq"][0]

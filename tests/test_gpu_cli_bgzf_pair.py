@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import common
-from test_gpu_cli_bgzf import first_reads, members, write_bgzf
+from test_gpu_cli_bgzf import first_reads, members, n_reads, write_bgzf
 from test_gpu_cli_text import CLI, blocks, run
 
 pytestmark = pytest.mark.gpu
@@ -70,6 +70,21 @@ def test_bgzf_mates_are_inflated_on_the_device_and_print_the_golden_output():
             b = run(args + ["-u", str(u), "--host-io"], t, tag="b")
             assert a[:2] == b[:2] and a[0] == first_reads(want[0], u), u
             assert members(a[2])[0] >= 1 and members(a[2])[1] == 0 and members(b[2]) is None, a[2]
+
+
+@pytest.mark.parametrize("window,printed", [(["-s", "13", "-u", "40"], 40), (["-s", "101"], 299)])
+def test_skip_and_upto_windows_on_bgzf_mates_print_what_the_host_threads_print(window, printed):
+    """-s beyond the first run's pairs (the first runs hold about nine of the 400): runs of which nothing is printed, then a run that
+    starts in its middle — and, with -u, one that ends in its middle"""
+    d, want, m1, m2 = golden_pair()
+    with tempfile.TemporaryDirectory() as t:
+        g1, g2 = write_bgzf(os.path.join(t, "r1.fa.gz"), m1), write_bgzf(os.path.join(t, "r2.fa.gz"), m2)
+        args = ["-f", "-t", "-p", "4", "-x", os.path.join(d, "idx"), "-1", g1, "-2", g2] + window
+        a = run(args + ALL, t, env=SMALL, tag="a")
+        b = run(args + ["--host-io"], t, tag="b")
+        assert a[0] == b[0], common.first_diff(a[0].decode("latin1"), b[0].decode("latin1"))
+        assert a[1] == b[1] and n_reads(b[0]) == printed
+        assert members(a[2])[0] >= 3 and members(a[2])[1] == 0 and members(b[2]) is None, a[2]
 
 
 def test_fastq_mates_and_columns_that_hold_the_reads_own_text():
