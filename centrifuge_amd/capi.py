@@ -199,6 +199,7 @@ EXPORTS = [
     "cf_kreport_enable", "cf_kreport_reset", "cf_kreport_get", "cf_kreport_write", "cf_batch_kreport_ms", "cf_batch_text_names",
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
+    "cf_debug_prim_scan",
 ]
 
 _lib = None
@@ -303,6 +304,7 @@ def lib():
         "cf_build_last_error": (cp, []),
         "cf_build_taxonomy": (i32, [C.POINTER(BuildInput), cp, C.c_char_p, u64]),
         "cf_build_describe": (i32, [C.POINTER(BuildInput), cp, C.c_char_p, u64]),
+        "cf_debug_prim_scan": (i32, [i32, i32, i32, vp, u64, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -994,6 +996,19 @@ def build_describe(fasta=None, codes=None, seq_off=None, seq_names=None):
     names = raw[o:e].split(b"\n")[:-1]
     text = np.frombuffer(raw, dtype=np.uint8, count=n, offset=e + 1)
     return {"len": n, "plen": plen, "rstarts": rst, "names": names, "text": text}
+
+
+def prim_scan(x, inclusive=False, device=0):
+    """The index builder's prefix sum on its own (cf_debug_prim_scan): x is uint32 or uint64; the sums wrap in that width."""
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.uint32, np.uint64):
+        raise TypeError("prim_scan takes uint32 or uint64")
+    out = np.empty_like(x)
+    L = lib()
+    st = L.cf_debug_prim_scan(device, x.dtype.itemsize, int(inclusive), x.ctypes.data, x.size, out.ctypes.data)
+    if st != 0:
+        raise CfError("%s: %s" % (L.cf_strerror(st).decode(), L.cf_build_last_error().decode()))
+    return out
 
 
 class Report:

@@ -836,4 +836,29 @@ cf_status cf_build_index(const cf_build_input *in, const char *outBase, int devi
     }
 }
 
+// The builder's prefix sum on its own (cf_prims.hpp), for tests: the device_scan instantiations buildOnGpu runs and no other —
+// u32 exclusive (tie compaction), u32 inclusive (group ids), u64 exclusive (occ of the sides).  Scratch sized as the builder sizes it.
+cf_status cf_debug_prim_scan(int device, int elem_bytes, int inclusive, const void *in, uint64_t n, void *out) {
+    const bool u32 = elem_bytes == 4, u64 = elem_bytes == 8 && !inclusive;
+    if ((n && (!in || !out)) || (!u32 && !u64)) { g_berr = "bad argument (the builder scans u32, exclusive or inclusive, and u64 exclusive)"; return CF_ERR_ARG; }
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { g_berr = "no HIP device visible"; return CF_ERR_NO_DEVICE; }
+    try {
+        HIPB(hipSetDevice(device));
+        Dev<uint8_t> dIn, dOut, tmp;
+        const size_t bytes = (size_t)n * (size_t)elem_bytes;
+        dIn.alloc(bytes); dOut.alloc(bytes);
+        tmp.alloc(u32 ? device_scan_bytes<uint32_t>(n) : device_scan_bytes<unsigned long long>(n));
+        if (n) HIPB(hipMemcpy(dIn.p, in, bytes, hipMemcpyHostToDevice));
+        if (u32 && inclusive) HIPB((device_scan<uint32_t, true>(tmp.p, reinterpret_cast<const uint32_t *>(dIn.p), reinterpret_cast<uint32_t *>(dOut.p), n)));
+        else if (u32) HIPB((device_scan<uint32_t, false>(tmp.p, reinterpret_cast<const uint32_t *>(dIn.p), reinterpret_cast<uint32_t *>(dOut.p), n)));
+        else HIPB((device_scan<unsigned long long, false>(tmp.p, reinterpret_cast<const unsigned long long *>(dIn.p), reinterpret_cast<unsigned long long *>(dOut.p), n)));
+        HIPB(hipDeviceSynchronize());
+        HIPB(hipGetLastError());
+        if (n) HIPB(hipMemcpy(out, dOut.p, bytes, hipMemcpyDeviceToHost));
+        return CF_OK;
+    } catch (const HipErr &e) { g_berr = e.what(); return CF_ERR_HIP;
+    } catch (const std::exception &e) { g_berr = e.what(); return CF_ERR_FORMAT; }
+}
+
 }  // extern "C"

@@ -62,6 +62,11 @@ cf_status cf_build_taxonomy(const cf_build_input *in, const char *out_base, char
  * <base>.1.cf are written from (bt2_io.h:854-880, bt2_idx.h:3262-3290, bt2_io.h:989-1027). */
 cf_status cf_build_describe(const cf_build_input *in, const char *path, char *err, uint64_t err_cap);
 
+/* The builder's prefix sum (cf_prims.hpp device_scan) on its own, for tests: n items of elem_bytes at `in` (host) -> n sums at
+ * `out` (host), out[i] = in[0] + .. + in[i-1] (inclusive = 0) or .. + in[i] (inclusive = 1), modulo 2^(8 elem_bytes).  Only the
+ * forms the builder runs exist: elem_bytes 4 with either, elem_bytes 8 with inclusive = 0; anything else is CF_ERR_ARG. */
+cf_status cf_debug_prim_scan(int device, int elem_bytes, int inclusive, const void *in, uint64_t n, void *out);
+
 /* The whole builder program as a call: the reference's own C symbol (centrifuge_build.cpp:550-556,
  * declared centrifuge_build_main.cpp:30-32).  argv as for centrifuge-build-bin; borrows argv;
  * returns non-zero with a message on stderr, never exits or throws. */
