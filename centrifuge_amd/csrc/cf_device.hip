@@ -2073,330 +2073,187 @@ static void uploadDense(cf_batch *bt, const cf_dense_reads *in, hipStream_t st) 
 }
 
 
-// a block of FASTA / FASTQ text (cf_text_reads): up as it is, then on the device — where its records start, the plain-form checks,
-// lengths, seeds and places per record (cf_textio.hpp) — and ONE wait for the status: the number of reads sizes the slot.  A block
-// that is not in the plain form leaves the slot without a batch (info->irregular says why): the caller's host parser takes it.
-static void uploadText(cf_batch *bt, const cf_text_reads *in, hipStream_t st, cf_text_info *info) {
-    if (in->format < CF_TEXT_FASTA || in->format > CF_TEXT_TAB6) throw ArgError("cf_text_reads::format is CF_TEXT_FASTA, CF_TEXT_FASTQ, CF_TEXT_TAB5 or CF_TEXT_TAB6");
-    const bool tab = in->format >= CF_TEXT_TAB5;
-    if (tab && in->text2) throw ArgError("a tabbed block holds both mates: cf_text_reads::text2 must be NULL");
-    const int nBlocks = in->text2 ? 2 : 1;
-    const char *src[2] = {in->text, in->text2};
-    const uint64_t nBs[2] = {in->n_bytes, in->text2 ? in->n_bytes2 : 0};
-    if ((nBs[0] && !src[0]) || (nBs[1] && !src[1])) throw ArgError("null text block");
-    if (nBs[0] + nBs[1] >= 0xffff0000ull) throw ArgError("the text blocks of a batch hold fewer than 2^32 bytes (32-bit places in them)");
-    const bool fasta = in->format == CF_TEXT_FASTA;
-    // The blocks lie one behind the other in one buffer, each followed by zero bytes; the per-piece counts, their sums and the marker
-    // places likewise.  Room for records of 32 bytes on average (a name and 22 bases take that): a block of shorter ones is the
-    // host parser's.
-    uint64_t at[2], pieces[2], pieceAt[2], recCap[2], posCap[2], posAt[2], textBytes = 0, nPieces = 0, posTotal = 0, recMax = 0;
+// Reads as text, one routine behind cf_batch_upload_text, _bgzf and _bgzf_pair.  A block (TextSource) is `head` bytes of text as
+// they are and, behind them, what its BGZF members inflate to; zi is where the entry reports on the members, nullptr for the blocks
+// of cf_batch_upload_text, which have none.  The blocks lie one behind the other in the slot's text buffer, each followed by zero
+// bytes; the per-piece counts, their sums and the marker places likewise.  On the device (cf_textio.hpp, cf_inflate.hpp): all
+// members of all blocks inflated by ONE launch, where the records of a block start, the plain-form checks, lengths, seeds and
+// places per record.
+//   plain blocks     ONE wait, for the status: the number of reads sizes the slot.
+//   blocks of members  nobody knows how many records a run of members holds before it is inflated: the text is cut behind its last
+//                    whole record (text_cut_body; two blocks behind the same number of records, text_cut_pair_body), what lies in
+//                    front of the cut is parsed, what lies behind it goes back to the caller in pinned memory, each file's of its
+//                    own.  TWO waits: for the inflater's status and the cut (the record pass is launched with them), and for the
+//                    parse.
+// A block that is not in the plain form leaves the slot without a batch (info->irregular says why): the caller's host parser takes
+// it.  So do a member that is corrupt (zi->corrupt) and a tail beyond its room.
+struct TextSource { const void *head; uint64_t headBytes; const void *members; uint64_t memberBytes; bool last; cf_bgzf_info *zi; };
+constexpr uint64_t kBgzfTailRoom = 1u << 20;
+static const char *const kTextTooLong = "the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)";
+static void uploadTextBlocks(cf_batch *bt, uint32_t format, uint32_t globalSeed, uint64_t maxReads, int nBlocks, const TextSource *src, hipStream_t st, cf_text_info *info) {
+    const bool fasta = format == CF_TEXT_FASTA, tab = format >= CF_TEXT_TAB5, cutting = src[0].zi != nullptr;
+    uint64_t inAt[2] = {0, 0}, inBytes = 0;                 // the members' bytes, each file's from an 8-byte boundary
+    for (int k = 0; k < nBlocks; k++) { inAt[k] = (inBytes + 7) & ~7ull; inBytes = inAt[k] + src[k].memberBytes; }
+    if (inBytes >= 0xffff0000ull) throw ArgError("the members of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
+    *info = cf_text_info{};
+    for (int k = 0; k < nBlocks; k++) if (src[k].zi) *src[k].zi = cf_bgzf_info{};
+    bt->loaded = false; bt->planned = false; bt->running = false; bt->finished = false;
+    // the members' headers and trailers, first for the sizes (the second text's place follows from the first one's size), then for the table
+    auto memberTable = [&](int k, uint64_t textAt, InfMember *out, uint64_t &n, uint64_t &inflated) {
+        try { return bgzf_member_table(static_cast<const uint8_t *>(src[k].members), src[k].memberBytes, inAt[k], textAt, out, n, inflated); }
+        catch (const std::length_error &) { throw ArgError(kTextTooLong); }
+    };
+    uint64_t nM[2] = {0, 0}, total[2] = {0, 0}, nMembers = 0;
     for (int k = 0; k < nBlocks; k++) {
-        at[k] = textBytes; pieces[k] = (nBs[k] + kTextPiece - 1) / kTextPiece; pieceAt[k] = nPieces;
-        recCap[k] = nBs[k] / 32 + 1024; posCap[k] = fasta ? recCap[k] : 4 * recCap[k]; posAt[k] = posTotal;
-        textBytes += pieces[k] * kTextPiece + kTextPad; nPieces += pieces[k] + 16; posTotal += posCap[k] + 16;
-        recMax = std::max(recMax, recCap[k]);
+        uint64_t inflated = 0;
+        if (src[k].zi && memberTable(k, 0, nullptr, nM[k], inflated) != kInfOk) { src[k].zi->corrupt = kInfHeader; src[k].zi->bad_member = (uint32_t)nM[k]; return; }
+        if (src[k].zi) src[k].zi->inflated_bytes = inflated;
+        total[k] = src[k].headBytes + inflated; nMembers += nM[k];
     }
+    if (total[0] + total[1] >= 0xffff0000ull) throw ArgError(kTextTooLong);
+    // room for records of 32 bytes on average (a name and 22 bases take that): a block of shorter ones is the host parser's
+    uint64_t at[2], pieces[2], pieceAt[2], recCap[2], posCap[2], posAt[2], textBytes = 0, nPieces = 0, posTotal = 0, recMax = 0, pieceMax = 0;
+    for (int k = 0; k < nBlocks; k++) {
+        at[k] = textBytes; pieces[k] = (total[k] + kTextPiece - 1) / kTextPiece; pieceAt[k] = nPieces;
+        recCap[k] = total[k] / 32 + 1024; posCap[k] = fasta ? recCap[k] : 4 * recCap[k]; posAt[k] = posTotal;
+        textBytes += pieces[k] * kTextPiece + kTextPad; nPieces += pieces[k] + 16; posTotal += posCap[k] + 16;
+        recMax = std::max(recMax, recCap[k]); pieceMax = std::max(pieceMax, pieces[k]);
+    }
+    if (textBytes >= 0xffffffffull) throw ArgError(kTextTooLong);
     const uint64_t readCap = recMax * (uint64_t)(tab ? 2 : nBlocks);            // (a tabbed record may be a pair)
     bt->text.ensure(textBytes);
     bt->txCnt.ensure(nPieces + 16); bt->txBase.ensure(nPieces + 16); bt->txPos.ensure(posTotal + 16);
-    bt->txTileA.ensure(scan_tiles_for(std::max(pieces[0], pieces[nBlocks - 1])) + 1); bt->txTileC.ensure(scan_tiles_for(std::max(pieces[0], pieces[nBlocks - 1])) + 1);
+    bt->txTileA.ensure(scan_tiles_for(pieceMax) + 1); bt->txTileC.ensure(scan_tiles_for(pieceMax) + 1);
     bt->rlen.ensure(readCap + 16); bt->seeds.ensure(readCap + 16);
     bt->txSeqOff.ensure(readCap + 16); bt->txIdOff.ensure(readCap + 16); bt->txIdLen.ensure(readCap + 16);
     if (!fasta) bt->txQualOff.ensure(readCap + 16);
     bt->txSt.ensure(1); bt->hTxSt.ensure(1); bt->hTxTotal.ensure(2);
-    *info = cf_text_info{};
-    bt->loaded = false; bt->planned = false; bt->running = false; bt->finished = false;
     HIP_OK(hipMemsetAsync(bt->txSt.p, 0, sizeof(TextStatus), st));
-    const uint32_t seed0 = (in->global_seed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
-    const dim3 bl(256);
+    if (cutting) {                                         // zCut / hZCut: per block its cut and the markers in front of it; hZCut + 4: the inflater's status
+        bt->zIn.ensure(inBytes + kInfPad + 8); bt->zMembers.ensure(nMembers + 1); bt->zErr.ensure(nMembers + 1); bt->zSt.ensure(1); bt->zCut.ensure(4);
+        bt->hZMembers.ensure(nMembers + 1); bt->hZCut.ensure(6); bt->hTail.ensure(kBgzfTailRoom + 16);
+        if (nBlocks == 2) bt->hTail2.ensure(kBgzfTailRoom + 16);
+        for (int k = 0; k < nBlocks; k++) { uint64_t inflated; (void)memberTable(k, at[k] + src[k].headBytes, bt->hZMembers.p + (k ? nM[0] : 0), nM[k], inflated); }
+        HIP_OK(hipMemsetAsync(bt->zSt.p, 0, sizeof(InfStatus), st));
+    }
     for (int k = 0; k < nBlocks; k++) {
         uint8_t *text = bt->text.p + at[k];
-        HIP_OK(hipMemsetAsync(text + nBs[k], 0, pieces[k] * kTextPiece + kTextPad - nBs[k], st));
-        if (nBs[k]) HIP_OK(hipMemcpyAsync(text, src[k], nBs[k], hipMemcpyHostToDevice, st));
-        uint32_t *cnt = bt->txCnt.p + pieceAt[k], *pos = bt->txPos.p + posAt[k];
+        HIP_OK(hipMemsetAsync(text + total[k], 0, pieces[k] * kTextPiece + kTextPad - total[k], st));
+        if (src[k].headBytes) HIP_OK(hipMemcpyAsync(text, src[k].head, src[k].headBytes, hipMemcpyHostToDevice, st));
+        if (nM[k]) HIP_OK(hipMemcpyAsync(bt->zIn.p + inAt[k], src[k].members, src[k].memberBytes, hipMemcpyHostToDevice, st));
+    }
+    if (nMembers) {
+        HIP_OK(hipMemcpyAsync(bt->zMembers.p, bt->hZMembers.p, nMembers * sizeof(InfMember), hipMemcpyHostToDevice, st));
+        const DInflate d{bt->zIn.p, bt->zMembers.p, (uint32_t)nMembers, bt->text.p, bt->zErr.p, bt->zSt.p, nullptr};
+        static const bool byLane = cfamd::cf_knob("CF_INFLATE_LANES") && std::atoi(cfamd::cf_knob("CF_INFLATE_LANES")) == 1;
+        if (byLane && nBlocks == 1) hipLaunchKernelGGL(k_inflate_lane, dim3((unsigned)((nMembers + 63) / 64)), dim3(64), 0, st, d);     // (the knob is the single-file entry's: cf_knobs.hpp)
+        else hipLaunchKernelGGL(k_inflate, dim3((unsigned)((nMembers + 256 / CF_WAVE - 1) / (256 / CF_WAVE))), dim3(256), 0, st, d);
+    }
+    const dim3 bl(256);
+    const uint32_t seed0 = (globalSeed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
+    auto blockPos = [&](int k) { return bt->txPos.p + posAt[k]; };
+    auto blockMarkers = [&](int k) { return bt->txBase.p + pieceAt[k] + pieces[k]; };       // (the scan's total: the block's markers)
+    auto mark = [&](int k) {
+        uint32_t *cnt = bt->txCnt.p + pieceAt[k];
         uint64_t *base = bt->txBase.p + pieceAt[k];
-        const DTextMark m{text, nBs[k], fasta ? (uint32_t)'>' : (uint32_t)'\n', cnt, base, pos, posCap[k]};
+        const DTextMark m{bt->text.p + at[k], total[k], fasta ? (uint32_t)'>' : (uint32_t)'\n', cnt, base, blockPos(k), posCap[k]};
         const dim3 gp((unsigned)std::max<uint64_t>(1, (pieces[k] + 255) / 256));
         if (pieces[k]) hipLaunchKernelGGL(k_text_count, gp, bl, 0, st, m);
         scan_enqueue<SCAN_PLAIN>(cnt, pieces[k], base, nullptr, bt->txTileA.p, bt->txTileC.p, st);
         if (pieces[k]) hipLaunchKernelGGL(k_text_mark, gp, bl, 0, st, m);
-        DTextRec d{text, nBs[k], pos, base + pieces[k], posCap[k], (uint32_t)recCap[k], (uint32_t)in->format, seed0,
-                   bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], (uint32_t)nBlocks, (uint32_t)k,
-                   fasta ? nullptr : bt->txQualOff.p, bt->textTrim5, bt->textTrim3, bt->textSkip};
+    };
+    auto records = [&](int k, uint64_t nBytes, const uint64_t *nMarkers) {
+        const DTextRec d{bt->text.p + at[k], nBytes, blockPos(k), nMarkers, posCap[k], (uint32_t)recCap[k], format, seed0,
+                         bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], (uint32_t)nBlocks, (uint32_t)k,
+                         fasta ? nullptr : bt->txQualOff.p, bt->textTrim5, bt->textTrim3, bt->textSkip};
         if (tab) hipLaunchKernelGGL(k_text_records_tab, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
         else hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
-        HIP_OK(hipMemcpyAsync(bt->hTxTotal.p + k, base + pieces[k], 8, hipMemcpyDeviceToHost, st));
+    };
+    uint64_t cut[2] = {total[0], total[1]};
+    uint8_t *const hTail[2] = {bt->hTail.p, bt->hTail2.p};
+    const uint64_t *hMarkers[2] = {bt->hTxTotal.p, bt->hTxTotal.p + 1};      // where the host finds a block's markers after the last wait
+    if (!cutting) {
+        for (int k = 0; k < nBlocks; k++) {
+            mark(k);
+            records(k, total[k], blockMarkers(k));
+            HIP_OK(hipMemcpyAsync(bt->hTxTotal.p + k, blockMarkers(k), 8, hipMemcpyDeviceToHost, st));
+        }
+    } else {
+        DTextCutPair cp{};
+        for (int k = 0; k < nBlocks; k++) {
+            mark(k);
+            cp.blk[k] = DTextCut{bt->text.p + at[k], total[k], blockPos(k), blockMarkers(k), posCap[k], fasta ? 0u : tab ? 2u : 1u, src[k].last ? 1u : 0u, bt->zCut.p + 2 * k};
+            hMarkers[k] = bt->hZCut.p + 2 * k + 1;
+        }
+        cp.flags = &bt->txSt.p->flags;
+        if (nBlocks == 2) hipLaunchKernelGGL(k_text_cut_pair, dim3(1), dim3(64), 0, st, cp);
+        else hipLaunchKernelGGL(k_text_cut, dim3(1), dim3(64), 0, st, cp.blk[0]);
+        HIP_OK(hipMemcpyAsync(bt->hZCut.p, bt->zCut.p, 16 * nBlocks, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(bt->hZCut.p + 4, bt->zSt.p, sizeof(InfStatus), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipGetLastError());
+        InfStatus zs; std::memcpy(&zs, bt->hZCut.p + 4, sizeof zs);
+        if (zs.bad) {
+            const uint64_t g = 0xffffffffu - zs.bad;                   // (its number among all blocks' members)
+            const int k = g < nM[0] ? 0 : 1;
+            cf_bgzf_info *z = src[k].zi;
+            z->bad_member = (uint32_t)(k ? g - nM[0] : g);
+            HIP_OK(hipMemcpy(&z->corrupt, bt->zErr.p + g, 4, hipMemcpyDeviceToHost));
+            if (!z->corrupt) z->corrupt = kInfBadCode;
+            return;
+        }
+        bool tailLeft = false, tailTooLong = false;
+        for (int k = 0; k < nBlocks; k++) {
+            cut[k] = bt->hZCut.p[2 * k];
+            if (cut[k] > total[k]) throw std::runtime_error("a text upload's cut lies behind its text");
+            tailLeft = tailLeft || cut[k] < total[k]; tailTooLong = tailTooLong || total[k] - cut[k] > kBgzfTailRoom;
+        }
+        // (both texts end here: with as many records in either, both are cut at their ends; else the longer one keeps a tail)
+        if (nBlocks == 2 && src[0].last && src[1].last && tailLeft) { info->irregular = kTxMateCount; return; }
+        if (tailTooLong) { info->irregular = kTxTailRoom; return; }
+        for (int k = 0; k < nBlocks; k++) if (total[k] > cut[k]) HIP_OK(hipMemcpyAsync(hTail[k], bt->text.p + at[k] + cut[k], total[k] - cut[k], hipMemcpyDeviceToHost, st));
+        for (int k = 0; k < nBlocks; k++) records(k, cut[k], bt->zCut.p + 2 * k + 1);
     }
     HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
     TextStatus ts = *bt->hTxSt.p;
     const bool tabPairs = tab && text_tab_kind(ts.flags);
-    uint64_t nRec[2] = {0, 0};
-    for (int k = 0; k < nBlocks; k++) nRec[k] = fasta || tab ? bt->hTxTotal.p[k] : bt->hTxTotal.p[k] >> 2;
     if (ts.flags) { info->irregular = ts.flags; return; }
-    if (nBlocks == 2 && nRec[0] != nRec[1]) { info->irregular = kTxMateCount; return; }
+    uint64_t nRec[2] = {0, 0};
+    for (int k = 0; k < nBlocks; k++) nRec[k] = fasta || tab ? *hMarkers[k] : *hMarkers[k] >> 2;
+    if (nBlocks == 2 && nRec[0] != nRec[1]) {
+        if (cutting) throw std::runtime_error("cf_batch_upload_bgzf_pair: the two cuts hold different numbers of records");
+        info->irregular = kTxMateCount; return;
+    }
     uint64_t nq = nRec[0] - std::min<uint64_t>(nRec[0], bt->textSkip);  // (cf_batch_set_text_skip: dropped before max_reads counts)
-    if (in->max_reads && nq > in->max_reads) nq = in->max_reads;     // (the sums below then cover a few reads too many: upper bounds, as they may be)
-    const uint64_t nReads = nq * (uint64_t)(tabPairs ? 2 : nBlocks);
-    sizeBatch(bt, nReads, ts.words(), ts.bases(), ts.maxLen, nBlocks == 2 || tabPairs);
+    if (maxReads && nq > maxReads) nq = maxReads;           // (the sums below then cover a few reads too many: upper bounds, as they may be)
+    const bool paired = nBlocks == 2 || tabPairs;
+    const uint64_t nReads = nq * (uint64_t)(paired ? 2 : 1);
+    sizeBatch(bt, nReads, ts.words(), ts.bases(), ts.maxLen, paired);
     bindBatch(bt);
     HIP_OK(hipEventRecord(bt->ev[8], st));
     bt->fromText = true; bt->fromBytes = false; bt->densePending = 0; bt->revMade = false; bt->nmaskZeroOf = nullptr;   // (k_text_pack writes every mask word)
     bt->textFastq = !fasta;
     bt->loaded = true;
-    info->n_reads = nReads; info->n_bases = ts.bases(); info->max_len = ts.maxLen; info->paired = nBlocks == 2 || tabPairs ? 1u : 0u;
-}
-
-// BGZF members (cf_bgzf_reads): the compressed bytes up, inflated on the device into the slot's text buffer behind the head the
-// caller hands in, the text cut behind its last whole record (text_cut_body) and everything in front of the cut parsed by the
-// passes of uploadText; what lies behind the cut goes back to the caller in pinned memory.  Two waits: for the inflater's
-// status and the cut (the record pass is launched with them), and for the parse.
-constexpr uint64_t kBgzfTailRoom = 1u << 20;
-static void uploadBgzf(cf_batch *bt, const cf_bgzf_reads *in, hipStream_t st, cf_text_info *info, cf_bgzf_info *zi) {
-    if (in->format < CF_TEXT_FASTA || in->format > CF_TEXT_TAB6) throw ArgError("cf_bgzf_reads::format is CF_TEXT_FASTA, CF_TEXT_FASTQ, CF_TEXT_TAB5 or CF_TEXT_TAB6");
-    const bool tab = in->format >= CF_TEXT_TAB5;
-    if ((in->n_bytes && !in->members) || (in->head_bytes && !in->head)) throw ArgError("null member / head bytes");
-    if (in->n_bytes >= 0xffff0000ull || in->head_bytes >= 0xffff0000ull) throw ArgError("the text of a batch holds fewer than 2^32 - 65536 bytes (32-bit places in it)");
-    *info = cf_text_info{}; *zi = cf_bgzf_info{};
-    bt->loaded = false; bt->planned = false; bt->running = false; bt->finished = false;
-    // the members' headers (the test BgzfImpl::fill applies, cf_bytesource.cpp) and trailers: where the payloads lie, where their text goes
-    const uint8_t *z = static_cast<const uint8_t *>(in->members);
-    uint64_t nMembers = 0;
-    for (uint64_t at = 0; at < in->n_bytes; nMembers++) {
-        if (in->n_bytes - at < 18) break;
-        at += (uint64_t)(z[at + 16] | (z[at + 17] << 8)) + 1;
-    }
-    bt->hZMembers.ensure(nMembers + 1);
-    uint64_t total = in->head_bytes, at = 0;
-    uint32_t m = 0;
-    for (; at < in->n_bytes; m++) {
-        const uint8_t *h = z + at;
-        bool ok = in->n_bytes - at >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4);
-        const uint64_t xlen = ok ? (uint64_t)(h[10] | (h[11] << 8)) : 0, bsize = ok ? (uint64_t)(h[16] | (h[17] << 8)) + 1 : 0;
-        ok = ok && xlen >= 6 && h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0 && bsize >= 12 + xlen + 8 && bsize <= in->n_bytes - at;
-        uint32_t crc = 0, isize = 0;
-        if (ok) { std::memcpy(&crc, h + bsize - 8, 4); std::memcpy(&isize, h + bsize - 4, 4); ok = isize <= kInfMaxOut; }
-        if (!ok) { zi->corrupt = kInfHeader; zi->bad_member = m; return; }
-        bt->hZMembers.p[m] = InfMember{(uint32_t)(at + 12 + xlen), (uint32_t)(bsize - 12 - xlen - 8), (uint32_t)total, isize, crc};
-        total += isize; at += bsize;
-        if (total >= 0xffff0000ull) throw ArgError("the text of a batch holds fewer than 2^32 - 65536 bytes (32-bit places in it)");
-    }
-    nMembers = m;
-    zi->inflated_bytes = total - in->head_bytes;
-    const bool fasta = in->format == CF_TEXT_FASTA;
-    const uint64_t pieces = (total + kTextPiece - 1) / kTextPiece, recCap = total / 32 + 1024, posCap = fasta ? recCap : 4 * recCap;
-    bt->text.ensure(pieces * kTextPiece + kTextPad);
-    bt->zIn.ensure(in->n_bytes + kInfPad + 8); bt->zMembers.ensure(nMembers + 1); bt->zErr.ensure(nMembers + 1); bt->zSt.ensure(1); bt->zCut.ensure(2);
-    bt->hZCut.ensure(4); bt->hTail.ensure(kBgzfTailRoom + 16);
-    bt->txCnt.ensure(pieces + 32); bt->txBase.ensure(pieces + 32); bt->txPos.ensure(posCap + 32);
-    bt->txTileA.ensure(scan_tiles_for(pieces) + 1); bt->txTileC.ensure(scan_tiles_for(pieces) + 1);
-    const uint64_t readCap = tab ? 2 * recCap : recCap;                          // (a tabbed record may be a pair)
-    bt->rlen.ensure(readCap + 16); bt->seeds.ensure(readCap + 16);
-    bt->txSeqOff.ensure(readCap + 16); bt->txIdOff.ensure(readCap + 16); bt->txIdLen.ensure(readCap + 16);
-    if (!fasta) bt->txQualOff.ensure(readCap + 16);
-    bt->txSt.ensure(1); bt->hTxSt.ensure(1); bt->hTxTotal.ensure(2);
-    HIP_OK(hipMemsetAsync(bt->txSt.p, 0, sizeof(TextStatus), st));
-    HIP_OK(hipMemsetAsync(bt->zSt.p, 0, sizeof(InfStatus), st));
-    uint8_t *text = bt->text.p;
-    HIP_OK(hipMemsetAsync(text + total, 0, pieces * kTextPiece + kTextPad - total, st));
-    if (in->head_bytes) HIP_OK(hipMemcpyAsync(text, in->head, in->head_bytes, hipMemcpyHostToDevice, st));
-    if (nMembers) {
-        HIP_OK(hipMemcpyAsync(bt->zIn.p, in->members, in->n_bytes, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(bt->zMembers.p, bt->hZMembers.p, nMembers * sizeof(InfMember), hipMemcpyHostToDevice, st));
-        const DInflate d{bt->zIn.p, bt->zMembers.p, (uint32_t)nMembers, text, bt->zErr.p, bt->zSt.p, nullptr};
-        static const bool byLane = cfamd::cf_knob("CF_INFLATE_LANES") && std::atoi(cfamd::cf_knob("CF_INFLATE_LANES")) == 1;
-        if (byLane) hipLaunchKernelGGL(k_inflate_lane, dim3((unsigned)((nMembers + 63) / 64)), dim3(64), 0, st, d);
-        else hipLaunchKernelGGL(k_inflate, dim3((unsigned)((nMembers + 256 / CF_WAVE - 1) / (256 / CF_WAVE))), dim3(256), 0, st, d);
-    }
-    const dim3 bl(256);
-    const DTextMark mk{text, total, fasta ? (uint32_t)'>' : (uint32_t)'\n', bt->txCnt.p, bt->txBase.p, bt->txPos.p, posCap};
-    const dim3 gp((unsigned)std::max<uint64_t>(1, (pieces + 255) / 256));
-    if (pieces) hipLaunchKernelGGL(k_text_count, gp, bl, 0, st, mk);
-    scan_enqueue<SCAN_PLAIN>(bt->txCnt.p, pieces, bt->txBase.p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
-    if (pieces) hipLaunchKernelGGL(k_text_mark, gp, bl, 0, st, mk);
-    const DTextCut ct{text, total, bt->txPos.p, bt->txBase.p + pieces, posCap, fasta ? 0u : tab ? 2u : 1u, in->last ? 1u : 0u, bt->zCut.p};
-    hipLaunchKernelGGL(k_text_cut, dim3(1), dim3(64), 0, st, ct);
-    HIP_OK(hipMemcpyAsync(bt->hZCut.p, bt->zCut.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(bt->hZCut.p + 2, bt->zSt.p, sizeof(InfStatus), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
-    InfStatus zs; std::memcpy(&zs, bt->hZCut.p + 2, sizeof zs);
-    if (zs.bad) {
-        zi->bad_member = 0xffffffffu - zs.bad;
-        HIP_OK(hipMemcpy(&zi->corrupt, bt->zErr.p + zi->bad_member, 4, hipMemcpyDeviceToHost));
-        if (!zi->corrupt) zi->corrupt = kInfBadCode;
-        return;
-    }
-    const uint64_t cut = bt->hZCut.p[0];
-    if (cut > total) throw std::runtime_error("cf_batch_upload_bgzf: the cut lies behind the text");
-    if (total - cut > kBgzfTailRoom) { info->irregular = kTxTailRoom; return; }
-    if (total > cut) HIP_OK(hipMemcpyAsync(bt->hTail.p, text + cut, total - cut, hipMemcpyDeviceToHost, st));
-    const uint32_t seed0 = (in->global_seed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
-    const DTextRec d{text, cut, bt->txPos.p, bt->zCut.p + 1, posCap, (uint32_t)recCap, (uint32_t)in->format, seed0,
-                     bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, 0u, 1u, 0u, fasta ? nullptr : bt->txQualOff.p,
-                     bt->textTrim5, bt->textTrim3, bt->textSkip};
-    if (tab) hipLaunchKernelGGL(k_text_records_tab, dim3((unsigned)((recCap + 255) / 256)), bl, 0, st, d);
-    else hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap + 255) / 256)), bl, 0, st, d);
-    HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
-    TextStatus ts = *bt->hTxSt.p;
-    const bool tabPairs = tab && text_tab_kind(ts.flags);
-    if (ts.flags) { info->irregular = ts.flags; return; }
-    uint64_t nq = fasta || tab ? bt->hZCut.p[1] : bt->hZCut.p[1] >> 2;
-    nq -= std::min<uint64_t>(nq, bt->textSkip);
-    if (in->max_reads && nq > in->max_reads) nq = in->max_reads;
-    sizeBatch(bt, tabPairs ? 2 * nq : nq, ts.words(), ts.bases(), ts.maxLen, tabPairs);
-    bindBatch(bt);
-    HIP_OK(hipEventRecord(bt->ev[8], st));
-    bt->fromText = true; bt->fromBytes = false; bt->densePending = 0; bt->revMade = false; bt->nmaskZeroOf = nullptr;
-    bt->textFastq = !fasta;
-    bt->loaded = true;
-    info->n_reads = tabPairs ? 2 * nq : nq; info->n_bases = ts.bases(); info->max_len = ts.maxLen; info->paired = tabPairs ? 1u : 0u;
-    zi->tail = reinterpret_cast<const char *>(bt->hTail.p); zi->tail_bytes = total - cut;
-}
-
-// The BGZF members of two mate files (cf_batch_upload_bgzf_pair): the two texts — head + inflate(members) of either file — lie one
-// behind the other in the slot's text buffer as the two blocks of uploadText do, all members are inflated by one launch, and both
-// texts are cut behind the same number of whole records (text_cut_pair_body): nobody knows how many records a run of members holds
-// before it is inflated.  Each file's tail goes back in pinned memory of its own.  The waits are uploadBgzf's.
-static bool bgzfMemberTable(const cf_bgzf_reads *in, uint64_t inAt, uint64_t textAt, InfMember *out, uint64_t &nMembers, uint64_t &total, cf_bgzf_info *zi) {
-    const uint8_t *z = static_cast<const uint8_t *>(in->members);
-    uint64_t at = 0;
-    uint32_t m = 0;
-    total = in->head_bytes;
-    for (; at < in->n_bytes; m++) {
-        const uint8_t *h = z + at;
-        bool ok = in->n_bytes - at >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4);
-        const uint64_t xlen = ok ? (uint64_t)(h[10] | (h[11] << 8)) : 0, bsize = ok ? (uint64_t)(h[16] | (h[17] << 8)) + 1 : 0;
-        ok = ok && xlen >= 6 && h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0 && bsize >= 12 + xlen + 8 && bsize <= in->n_bytes - at;
-        uint32_t crc = 0, isize = 0;
-        if (ok) { std::memcpy(&crc, h + bsize - 8, 4); std::memcpy(&isize, h + bsize - 4, 4); ok = isize <= kInfMaxOut; }
-        if (!ok) { zi->corrupt = kInfHeader; zi->bad_member = m; return false; }
-        if (out) out[m] = InfMember{(uint32_t)(inAt + at + 12 + xlen), (uint32_t)(bsize - 12 - xlen - 8), (uint32_t)(textAt + total), isize, crc};
-        total += isize; at += bsize;
-        if (total >= 0xffff0000ull) throw ArgError("the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
-    }
-    nMembers = m;
-    return true;
-}
-static void uploadBgzfPair(cf_batch *bt, const cf_bgzf_reads *in1, const cf_bgzf_reads *in2, hipStream_t st, cf_text_info *info, cf_bgzf_info *z1, cf_bgzf_info *z2) {
-    const cf_bgzf_reads *in[2] = {in1, in2};
-    cf_bgzf_info *zi[2] = {z1, z2};
-    if (in1->format != CF_TEXT_FASTA && in1->format != CF_TEXT_FASTQ) throw ArgError("cf_bgzf_reads::format is CF_TEXT_FASTA or CF_TEXT_FASTQ");
-    if (in2->format != in1->format || in2->global_seed != in1->global_seed || in2->max_reads != in1->max_reads)
-        throw ArgError("cf_batch_upload_bgzf_pair: format, global_seed and max_reads are the first mate's; the second mate's differ");
-    for (int k = 0; k < 2; k++) {
-        if ((in[k]->n_bytes && !in[k]->members) || (in[k]->head_bytes && !in[k]->head)) throw ArgError("null member / head bytes");
-        if (in[k]->n_bytes >= 0xffff0000ull || in[k]->head_bytes >= 0xffff0000ull) throw ArgError("the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
-    }
-    const uint64_t inAt[2] = {0, (in1->n_bytes + 7) & ~7ull}, inBytes = inAt[1] + in2->n_bytes;
-    if (inBytes >= 0xffff0000ull) throw ArgError("the members of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
-    *info = cf_text_info{}; *z1 = cf_bgzf_info{}; *z2 = cf_bgzf_info{};
-    bt->loaded = false; bt->planned = false; bt->running = false; bt->finished = false;
-    // the members' headers and trailers, first for the sizes (the second text's place follows from the first one's size), then for the table
-    uint64_t nM[2] = {0, 0}, total[2] = {0, 0};
-    for (int k = 0; k < 2; k++) if (!bgzfMemberTable(in[k], 0, 0, nullptr, nM[k], total[k], zi[k])) return;
-    if (total[0] + total[1] >= 0xffff0000ull) throw ArgError("the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
-    const bool fasta = in1->format == CF_TEXT_FASTA;
-    uint64_t at[2], pieces[2], pieceAt[2], recCap[2], posCap[2], posAt[2], textBytes = 0, nPieces = 0, posTotal = 0, recMax = 0;
-    for (int k = 0; k < 2; k++) {
-        at[k] = textBytes; pieces[k] = (total[k] + kTextPiece - 1) / kTextPiece; pieceAt[k] = nPieces;
-        recCap[k] = total[k] / 32 + 1024; posCap[k] = fasta ? recCap[k] : 4 * recCap[k]; posAt[k] = posTotal;
-        textBytes += pieces[k] * kTextPiece + kTextPad; nPieces += pieces[k] + 16; posTotal += posCap[k] + 16;
-        recMax = std::max(recMax, recCap[k]);
-    }
-    if (textBytes >= 0xffffffffull) throw ArgError("the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)");
-    const uint64_t nMembers = nM[0] + nM[1];
-    bt->hZMembers.ensure(nMembers + 1);
-    for (int k = 0; k < 2; k++) (void)bgzfMemberTable(in[k], inAt[k], at[k], bt->hZMembers.p + (k ? nM[0] : 0), nM[k], total[k], zi[k]);
-    for (int k = 0; k < 2; k++) zi[k]->inflated_bytes = total[k] - in[k]->head_bytes;
-    const uint64_t readCap = 2 * recMax;
-    bt->text.ensure(textBytes);
-    bt->zIn.ensure(inBytes + kInfPad + 8); bt->zMembers.ensure(nMembers + 1); bt->zErr.ensure(nMembers + 1); bt->zSt.ensure(1); bt->zCut.ensure(4);
-    bt->hZCut.ensure(6); bt->hTail.ensure(kBgzfTailRoom + 16); bt->hTail2.ensure(kBgzfTailRoom + 16);
-    bt->txCnt.ensure(nPieces + 16); bt->txBase.ensure(nPieces + 16); bt->txPos.ensure(posTotal + 16);
-    bt->txTileA.ensure(scan_tiles_for(std::max(pieces[0], pieces[1])) + 1); bt->txTileC.ensure(scan_tiles_for(std::max(pieces[0], pieces[1])) + 1);
-    bt->rlen.ensure(readCap + 16); bt->seeds.ensure(readCap + 16);
-    bt->txSeqOff.ensure(readCap + 16); bt->txIdOff.ensure(readCap + 16); bt->txIdLen.ensure(readCap + 16);
-    if (!fasta) bt->txQualOff.ensure(readCap + 16);
-    bt->txSt.ensure(1); bt->hTxSt.ensure(1); bt->hTxTotal.ensure(2);
-    HIP_OK(hipMemsetAsync(bt->txSt.p, 0, sizeof(TextStatus), st));
-    HIP_OK(hipMemsetAsync(bt->zSt.p, 0, sizeof(InfStatus), st));
-    for (int k = 0; k < 2; k++) {
-        uint8_t *text = bt->text.p + at[k];
-        HIP_OK(hipMemsetAsync(text + total[k], 0, pieces[k] * kTextPiece + kTextPad - total[k], st));
-        if (in[k]->head_bytes) HIP_OK(hipMemcpyAsync(text, in[k]->head, in[k]->head_bytes, hipMemcpyHostToDevice, st));
-        if (nM[k]) HIP_OK(hipMemcpyAsync(bt->zIn.p + inAt[k], in[k]->members, in[k]->n_bytes, hipMemcpyHostToDevice, st));
-    }
-    if (nMembers) {
-        HIP_OK(hipMemcpyAsync(bt->zMembers.p, bt->hZMembers.p, nMembers * sizeof(InfMember), hipMemcpyHostToDevice, st));
-        const DInflate d{bt->zIn.p, bt->zMembers.p, (uint32_t)nMembers, bt->text.p, bt->zErr.p, bt->zSt.p, nullptr};
-        hipLaunchKernelGGL(k_inflate, dim3((unsigned)((nMembers + 256 / CF_WAVE - 1) / (256 / CF_WAVE))), dim3(256), 0, st, d);
-    }
-    const dim3 bl(256);
-    DTextCutPair cp{};
-    for (int k = 0; k < 2; k++) {
-        uint8_t *text = bt->text.p + at[k];
-        uint32_t *cnt = bt->txCnt.p + pieceAt[k], *pos = bt->txPos.p + posAt[k];
-        uint64_t *base = bt->txBase.p + pieceAt[k];
-        const DTextMark mk{text, total[k], fasta ? (uint32_t)'>' : (uint32_t)'\n', cnt, base, pos, posCap[k]};
-        const dim3 gp((unsigned)std::max<uint64_t>(1, (pieces[k] + 255) / 256));
-        if (pieces[k]) hipLaunchKernelGGL(k_text_count, gp, bl, 0, st, mk);
-        scan_enqueue<SCAN_PLAIN>(cnt, pieces[k], base, nullptr, bt->txTileA.p, bt->txTileC.p, st);
-        if (pieces[k]) hipLaunchKernelGGL(k_text_mark, gp, bl, 0, st, mk);
-        cp.blk[k] = DTextCut{text, total[k], pos, base + pieces[k], posCap[k], fasta ? 0u : 1u, in[k]->last ? 1u : 0u, bt->zCut.p + 2 * k};
-    }
-    cp.flags = &bt->txSt.p->flags;
-    hipLaunchKernelGGL(k_text_cut_pair, dim3(1), dim3(64), 0, st, cp);
-    HIP_OK(hipMemcpyAsync(bt->hZCut.p, bt->zCut.p, 32, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(bt->hZCut.p + 4, bt->zSt.p, sizeof(InfStatus), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
-    InfStatus zs; std::memcpy(&zs, bt->hZCut.p + 4, sizeof zs);
-    if (zs.bad) {
-        const uint64_t g = 0xffffffffu - zs.bad;                       // (its number among both files' members)
-        cf_bgzf_info *z = g < nM[0] ? z1 : z2;
-        z->bad_member = (uint32_t)(g < nM[0] ? g : g - nM[0]);
-        HIP_OK(hipMemcpy(&z->corrupt, bt->zErr.p + g, 4, hipMemcpyDeviceToHost));
-        if (!z->corrupt) z->corrupt = kInfBadCode;
-        return;
-    }
-    const uint64_t cut[2] = {bt->hZCut.p[0], bt->hZCut.p[2]}, nMark[2] = {bt->hZCut.p[1], bt->hZCut.p[3]};
-    if (cut[0] > total[0] || cut[1] > total[1]) throw std::runtime_error("cf_batch_upload_bgzf_pair: a cut lies behind its text");
-    // (both texts end here: with as many records in either, both are cut at their ends; else the longer one keeps a tail)
-    if (in1->last && in2->last && (cut[0] < total[0] || cut[1] < total[1])) { info->irregular = kTxMateCount; return; }
-    if (total[0] - cut[0] > kBgzfTailRoom || total[1] - cut[1] > kBgzfTailRoom) { info->irregular = kTxTailRoom; return; }
-    uint8_t *hTail[2] = {bt->hTail.p, bt->hTail2.p};
-    for (int k = 0; k < 2; k++) if (total[k] > cut[k]) HIP_OK(hipMemcpyAsync(hTail[k], bt->text.p + at[k] + cut[k], total[k] - cut[k], hipMemcpyDeviceToHost, st));
-    const uint32_t seed0 = (in1->global_seed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
-    for (int k = 0; k < 2; k++) {
-        const DTextRec d{bt->text.p + at[k], cut[k], bt->txPos.p + posAt[k], bt->zCut.p + 2 * k + 1, posCap[k], (uint32_t)recCap[k], (uint32_t)in1->format, seed0,
-                         bt->rlen.p, bt->seeds.p, bt->txSeqOff.p, bt->txIdOff.p, bt->txIdLen.p, bt->txSt.p, (uint32_t)at[k], 2u, (uint32_t)k,
-                         fasta ? nullptr : bt->txQualOff.p, bt->textTrim5, bt->textTrim3, bt->textSkip};
-        hipLaunchKernelGGL(k_text_records, dim3((unsigned)((recCap[k] + 255) / 256)), bl, 0, st, d);
-    }
-    HIP_OK(hipMemcpyAsync(bt->hTxSt.p, bt->txSt.p, sizeof(TextStatus), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipGetLastError());
-    const TextStatus ts = *bt->hTxSt.p;
-    if (ts.flags) { info->irregular = ts.flags; return; }
-    uint64_t nq = fasta ? nMark[0] : nMark[0] >> 2;
-    if (nq != (fasta ? nMark[1] : nMark[1] >> 2)) throw std::runtime_error("cf_batch_upload_bgzf_pair: the two cuts hold different numbers of records");
-    nq -= std::min<uint64_t>(nq, bt->textSkip);
-    if (in1->max_reads && nq > in1->max_reads) nq = in1->max_reads;
-    sizeBatch(bt, 2 * nq, ts.words(), ts.bases(), ts.maxLen, true);
-    bindBatch(bt);
-    HIP_OK(hipEventRecord(bt->ev[8], st));
-    bt->fromText = true; bt->fromBytes = false; bt->densePending = 0; bt->revMade = false; bt->nmaskZeroOf = nullptr;
-    bt->textFastq = !fasta;
-    bt->loaded = true;
-    info->n_reads = 2 * nq; info->n_bases = ts.bases(); info->max_len = ts.maxLen;
-    for (int k = 0; k < 2; k++) { zi[k]->tail = reinterpret_cast<const char *>(hTail[k]); zi[k]->tail_bytes = total[k] - cut[k]; }
+    info->n_reads = nReads; info->n_bases = ts.bases(); info->max_len = ts.maxLen; info->paired = paired ? 1u : 0u;
+    if (cutting) for (int k = 0; k < nBlocks; k++) { src[k].zi->tail = reinterpret_cast<const char *>(hTail[k]); src[k].zi->tail_bytes = total[k] - cut[k]; }
 }
 
 // ======================================================================= batch C ABI
+// what every cf_batch_upload* does first
+static void beginUpload(cf_batch *bt) {
+    HIP_OK(hipSetDevice(bt->cl->ix->device));
+    if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
+}
+// ... and every wait last: after a failure the batch is lost, and the slot takes the next one
+static cf_status endWait(cf_batch *bt, cf_status rc) {
+    if (rc != CF_OK) {
+        (void)hipStreamSynchronize(bt->stream);
+        bt->running = false; bt->finished = false;
+    }
+    return rc;
+}
 cf_status cf_host_alloc(void **p, size_t bytes) {
     if (!p) return CF_ERR_ARG;
     *p = nullptr;
@@ -2449,8 +2306,7 @@ cf_status cf_slot_estimate_bytes(uint64_t maxReads, uint64_t maxWords, int khits
 cf_status cf_batch_upload_packed_async(cf_batch *bt, const cf_packed_reads *in, void *streamv) {
     if (!bt || !in) return CF_ERR_ARG;
     return guard([&] {
-        HIP_OK(hipSetDevice(bt->cl->ix->device));
-        if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
+        beginUpload(bt);
         uploadPacked(bt, in, static_cast<hipStream_t>(streamv));
     });
 }
@@ -2458,8 +2314,7 @@ cf_status cf_batch_upload_packed_async(cf_batch *bt, const cf_packed_reads *in, 
 cf_status cf_batch_upload_dense_async(cf_batch *bt, const cf_dense_reads *in, void *streamv) {
     if (!bt || !in) return CF_ERR_ARG;
     return guard([&] {
-        HIP_OK(hipSetDevice(bt->cl->ix->device));
-        if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
+        beginUpload(bt);
         uploadDense(bt, in, static_cast<hipStream_t>(streamv));
     });
 }
@@ -2537,11 +2392,7 @@ cf_status cf_batch_wait_narrow(cf_batch *bt, cf_results_narrow *res) {
             res->slow_post = bt->hSt.p->nSlowPost; res->slow_score = bt->hSt.p->nSlowScore;
         }
     });
-    if (rc != CF_OK) {                                     // the batch is lost; the slot takes the next one
-        (void)hipStreamSynchronize(bt->stream);
-        bt->running = false; bt->finished = false;
-    }
-    return rc;
+    return endWait(bt, rc);
 }
 
 uint32_t cf_narrow_max_score(uint8_t qinfo, uint32_t len1, uint32_t len2, int paired) {
@@ -2586,37 +2437,48 @@ cf_status cf_batch_wait(cf_batch *bt, cf_results *res) {
             res->slow_post = bt->hSt.p->nSlowPost; res->slow_score = bt->hSt.p->nSlowScore;
         }
     });
-    if (rc != CF_OK) {                                     // the batch is lost; the slot takes the next one
-        (void)hipStreamSynchronize(bt->stream);
-        bt->running = false; bt->finished = false;
-    }
-    return rc;
+    return endWait(bt, rc);
 }
 
 cf_status cf_batch_upload_text(cf_batch *bt, const cf_text_reads *in, void *streamv, cf_text_info *info) {
     if (!bt || !in || !info) return CF_ERR_ARG;
     return guard([&] {
-        HIP_OK(hipSetDevice(bt->cl->ix->device));
-        if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
-        uploadText(bt, in, static_cast<hipStream_t>(streamv), info);
+        beginUpload(bt);
+        if (in->format < CF_TEXT_FASTA || in->format > CF_TEXT_TAB6) throw ArgError("cf_text_reads::format is CF_TEXT_FASTA, CF_TEXT_FASTQ, CF_TEXT_TAB5 or CF_TEXT_TAB6");
+        if (in->format >= CF_TEXT_TAB5 && in->text2) throw ArgError("a tabbed block holds both mates: cf_text_reads::text2 must be NULL");
+        const TextSource src[2] = {{in->text, in->n_bytes, nullptr, 0, true, nullptr}, {in->text2, in->text2 ? in->n_bytes2 : 0, nullptr, 0, true, nullptr}};
+        if ((src[0].headBytes && !src[0].head) || (src[1].headBytes && !src[1].head)) throw ArgError("null text block");
+        if (src[0].headBytes + src[1].headBytes >= 0xffff0000ull) throw ArgError(kTextTooLong);
+        uploadTextBlocks(bt, (uint32_t)in->format, in->global_seed, in->max_reads, in->text2 ? 2 : 1, src, static_cast<hipStream_t>(streamv), info);
     });
+}
+
+// (the argument rules of a cf_bgzf_reads, either entry's)
+static TextSource bgzfSource(const cf_bgzf_reads *in, cf_bgzf_info *zi) {
+    if ((in->n_bytes && !in->members) || (in->head_bytes && !in->head)) throw ArgError("null member / head bytes");
+    if (in->n_bytes >= 0xffff0000ull || in->head_bytes >= 0xffff0000ull) throw ArgError(kTextTooLong);
+    return TextSource{in->head, in->head_bytes, in->members, in->n_bytes, in->last != 0, zi};
 }
 
 cf_status cf_batch_upload_bgzf(cf_batch *bt, const cf_bgzf_reads *in, void *streamv, cf_text_info *info, cf_bgzf_info *zi) {
     if (!bt || !in || !info || !zi) return CF_ERR_ARG;
     return guard([&] {
-        HIP_OK(hipSetDevice(bt->cl->ix->device));
-        if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
-        uploadBgzf(bt, in, static_cast<hipStream_t>(streamv), info, zi);
+        beginUpload(bt);
+        if (in->format < CF_TEXT_FASTA || in->format > CF_TEXT_TAB6) throw ArgError("cf_bgzf_reads::format is CF_TEXT_FASTA, CF_TEXT_FASTQ, CF_TEXT_TAB5 or CF_TEXT_TAB6");
+        const TextSource src = bgzfSource(in, zi);
+        uploadTextBlocks(bt, (uint32_t)in->format, in->global_seed, in->max_reads, 1, &src, static_cast<hipStream_t>(streamv), info);
     });
 }
 
 cf_status cf_batch_upload_bgzf_pair(cf_batch *bt, const cf_bgzf_reads *mate1, const cf_bgzf_reads *mate2, void *streamv, cf_text_info *info, cf_bgzf_info *z1, cf_bgzf_info *z2) {
     if (!bt || !mate1 || !mate2 || !info || !z1 || !z2) return CF_ERR_ARG;
     return guard([&] {
-        HIP_OK(hipSetDevice(bt->cl->ix->device));
-        if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
-        uploadBgzfPair(bt, mate1, mate2, static_cast<hipStream_t>(streamv), info, z1, z2);
+        beginUpload(bt);
+        if (mate1->format != CF_TEXT_FASTA && mate1->format != CF_TEXT_FASTQ) throw ArgError("cf_bgzf_reads::format is CF_TEXT_FASTA or CF_TEXT_FASTQ");
+        if (mate2->format != mate1->format || mate2->global_seed != mate1->global_seed || mate2->max_reads != mate1->max_reads)
+            throw ArgError("cf_batch_upload_bgzf_pair: format, global_seed and max_reads are the first mate's; the second mate's differ");
+        const TextSource src[2] = {bgzfSource(mate1, z1), bgzfSource(mate2, z2)};
+        uploadTextBlocks(bt, (uint32_t)mate1->format, mate1->global_seed, mate1->max_reads, 2, src, static_cast<hipStream_t>(streamv), info);
     });
 }
 
@@ -2721,6 +2583,29 @@ cf_status cf_batch_set_text_skip(cf_batch *bt, uint64_t skipReads) {
     return CF_OK;
 }
 
+// CF_BGZF_OUT_MEMBER (cf_knobs.hpp): the text bytes per member of every BGZF output; false: not a size a member takes (g_err says so)
+static bool bgzfOutMember(uint32_t &member) {
+    member = kDefMember;
+    if (const char *v = cfamd::cf_knob("CF_BGZF_OUT_MEMBER")) member = (uint32_t)std::strtoul(v, nullptr, 10);
+    if (def_member_ok(member)) return true;
+    g_err = "CF_BGZF_OUT_MEMBER: a multiple of 64, from 64 to 65280";
+    return false;
+}
+// Queued on st: text[0, nBytes) deflated into nMembers members (cf_deflate.hpp) that lie in z at their stride, their sizes summed, the
+// members moved together into the room the text lay in (it has been read by then) and the sum sent to *hTotal.  ev: two events
+// around k_deflate, or nullptr.  The caller waits, for as many of these as it queued.
+static void enqueueDeflate(uint8_t *text, uint64_t nBytes, uint32_t member, uint64_t nMembers, uint8_t *z, uint32_t *zSize, uint64_t *zOff,
+                           uint64_t *tileA, uint32_t *tileC, uint64_t *hTotal, hipEvent_t *ev, hipStream_t st) {
+    const DDeflate d{text, nBytes, member, (uint32_t)nMembers, z, zSize};
+    if (ev) HIP_OK(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_deflate, dim3((unsigned)((nMembers + 1) / 2)), dim3(2 * CF_WAVE), 0, st, d);
+    if (ev) HIP_OK(hipEventRecord(ev[1], st));
+    scan_enqueue<SCAN_PLAIN>(zSize, nMembers, zOff, nullptr, tileA, tileC, st);
+    const DDefCompact dc{z, def_stride(member), (uint32_t)nMembers, zSize, zOff, text};
+    hipLaunchKernelGGL(k_deflate_compact, dim3((unsigned)nMembers), dim3(256), 0, st, dc);
+    HIP_OK(hipMemcpyAsync(hTotal, zOff + nMembers, 8, hipMemcpyDeviceToHost, st));
+}
+
 // The results of a batch that came as text, as text: the default columns formatted on the device from the rows the kernels left
 // there (none of them crosses the link), and the perfect multi-assignment tuples the report's EM needs beside the device's counters.
 static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_t *textBytes) {
@@ -2733,10 +2618,7 @@ static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_
         return CF_ERR_ARG;
     }
     uint32_t member = kDefMember;
-    if (bgzf) {
-        if (const char *v = cfamd::cf_knob("CF_BGZF_OUT_MEMBER")) member = (uint32_t)std::strtoul(v, nullptr, 10);
-        if (!def_member_ok(member)) { g_err = "CF_BGZF_OUT_MEMBER: a multiple of 64, from 64 to 65280"; return CF_ERR_ARG; }
-    }
+    if (bgzf && !bgzfOutMember(member)) return CF_ERR_ARG;
     const cf_status rc = guard([&] {
         cf_classifier *cl = bt->cl;
         HIP_OK(hipSetDevice(cl->ix->device));
@@ -2809,15 +2691,8 @@ static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_
             if (bgzf && nMembers) {
                 bt->zOut.ensure(nMembers * def_stride(member)); bt->zOutSize.ensure(nMembers + 16); bt->zOutOff.ensure(nMembers + 16);
                 bt->txTileA.ensure(scan_tiles_for(nMembers) + 1); bt->txTileC.ensure(scan_tiles_for(nMembers) + 1);
-                const DDeflate d{bt->textOut.p, total, member, (uint32_t)nMembers, bt->zOut.p, bt->zOutSize.p};
                 for (auto &e : bt->evDef) if (!e) HIP_OK(hipEventCreate(&e));
-                HIP_OK(hipEventRecord(bt->evDef[0], st));
-                hipLaunchKernelGGL(k_deflate, dim3((unsigned)((nMembers + 1) / 2)), dim3(2 * CF_WAVE), 0, st, d);
-                HIP_OK(hipEventRecord(bt->evDef[1], st));
-                scan_enqueue<SCAN_PLAIN>(bt->zOutSize.p, nMembers, bt->zOutOff.p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
-                const DDefCompact dc{bt->zOut.p, def_stride(member), (uint32_t)nMembers, bt->zOutSize.p, bt->zOutOff.p, bt->textOut.p};
-                hipLaunchKernelGGL(k_deflate_compact, dim3((unsigned)nMembers), dim3(256), 0, st, dc);
-                HIP_OK(hipMemcpyAsync(bt->hTxTotal.p, bt->zOutOff.p + nMembers, 8, hipMemcpyDeviceToHost, st));
+                enqueueDeflate(bt->textOut.p, total, member, nMembers, bt->zOut.p, bt->zOutSize.p, bt->zOutOff.p, bt->txTileA.p, bt->txTileC.p, bt->hTxTotal.p, bt->evDef, st);
                 HIP_OK(hipStreamSynchronize(st));
                 total = *bt->hTxTotal.p;
                 if (total > nMembers * def_stride(member)) throw std::logic_error("the BGZF members outgrew their room");
@@ -2841,11 +2716,7 @@ static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_
         res->n_queries = nq; res->total_rows = bt->rowsOut; res->planned_sa_rows = bt->rowsTotal; res->row_passes = bt->passes;
         res->slow_post = bt->hSt.p->nSlowPost; res->slow_score = bt->hSt.p->nSlowScore;
     });
-    if (rc != CF_OK) {                                     // the batch is lost; the slot takes the next one
-        (void)hipStreamSynchronize(bt->stream);
-        bt->running = false; bt->finished = false;
-    }
-    return rc;
+    return endWait(bt, rc);
 }
 
 cf_status cf_batch_wait_text(cf_batch *bt, cf_results_text *res) { return waitText(bt, res, false, nullptr); }
@@ -2868,10 +2739,7 @@ cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
     if (!bt->splitSinks) { g_err = "cf_batch_wait_text_split: no split is set (cf_batch_set_text_split)"; return CF_ERR_ARG; }
     if (!bt->finished || !bt->textDone) { g_err = "cf_batch_wait_text_split: the batch has not been waited for with cf_batch_wait_text / cf_batch_wait_text_bgzf"; return CF_ERR_ARG; }
     uint32_t member = kDefMember;
-    if (bt->splitBgzf) {
-        if (const char *v = cfamd::cf_knob("CF_BGZF_OUT_MEMBER")) member = (uint32_t)std::strtoul(v, nullptr, 10);
-        if (!def_member_ok(member)) { g_err = "CF_BGZF_OUT_MEMBER: a multiple of 64, from 64 to 65280"; return CF_ERR_ARG; }
-    }
+    if (bt->splitBgzf && !bgzfOutMember(member)) return CF_ERR_ARG;
     const cf_status rc = guard([&] {
         cf_classifier *cl = bt->cl;
         HIP_OK(hipSetDevice(cl->ix->device));
@@ -2937,12 +2805,7 @@ cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
                     const uint64_t total = tot[s], nm = nMembers[s];
                     if (!bgzf) { bt->spBytes[s] = total; if (total) HIP_OK(hipMemcpyAsync(bt->hSpOut[s].p, bt->spOut[s].p, total, hipMemcpyDeviceToHost, st)); continue; }
                     if (!nm) continue;
-                    const DDeflate dd{bt->spOut[s].p, total, member, (uint32_t)nm, bt->spZ[s].p, bt->spZSize[s].p};
-                    hipLaunchKernelGGL(k_deflate, dim3((unsigned)((nm + 1) / 2)), dim3(2 * CF_WAVE), 0, st, dd);
-                    scan_enqueue<SCAN_PLAIN>(bt->spZSize[s].p, nm, bt->spZOff[s].p, nullptr, bt->spTileA[s].p, bt->spTileC[s].p, st);
-                    const DDefCompact dc{bt->spZ[s].p, def_stride(member), (uint32_t)nm, bt->spZSize[s].p, bt->spZOff[s].p, bt->spOut[s].p};
-                    hipLaunchKernelGGL(k_deflate_compact, dim3((unsigned)nm), dim3(256), 0, st, dc);
-                    HIP_OK(hipMemcpyAsync(tot + 2 * kSplitSinks + s, bt->spZOff[s].p + nm, 8, hipMemcpyDeviceToHost, st));
+                    enqueueDeflate(bt->spOut[s].p, total, member, nm, bt->spZ[s].p, bt->spZSize[s].p, bt->spZOff[s].p, bt->spTileA[s].p, bt->spTileC[s].p, tot + 2 * kSplitSinks + s, nullptr, st);
                 }
                 if (bgzf) {
                     HIP_OK(hipStreamSynchronize(st));
@@ -2992,9 +2855,8 @@ void cf_bgzf_eof(uint8_t out[28]) {
 // The same container from text the host holds: zlib's raw deflate at level 1, members of the same size (and knob) as the device's.
 cf_status cf_bgzf_deflate_host(const char *text, uint64_t n, void *outv, uint64_t cap, uint64_t *outBytes) {
     if ((n && !text) || !outBytes || (cap && !outv)) return CF_ERR_ARG;
-    uint32_t member = kDefMember;
-    if (const char *v = cfamd::cf_knob("CF_BGZF_OUT_MEMBER")) member = (uint32_t)std::strtoul(v, nullptr, 10);
-    if (!def_member_ok(member)) { g_err = "CF_BGZF_OUT_MEMBER: a multiple of 64, from 64 to 65280"; return CF_ERR_ARG; }
+    uint32_t member;
+    if (!bgzfOutMember(member)) return CF_ERR_ARG;
     uint8_t *out = static_cast<uint8_t *>(outv);
     uint64_t at = 0;
     std::vector<uint8_t> buf(member + 64);
@@ -3052,8 +2914,7 @@ cf_status cf_batch_create(cf_classifier *cl, const uint8_t *seq, const uint64_t 
 cf_status cf_batch_upload(cf_batch *bt, const uint8_t *seq, const uint64_t *off, const uint32_t *seeds, uint64_t nReads, int paired, void *streamv) {
     if (!bt || !off || !seeds || (paired && (nReads & 1))) return CF_ERR_ARG;
     return guard([&] {
-        HIP_OK(hipSetDevice(bt->cl->ix->device));
-        if (bt->running && !bt->finished) throw ArgError("the slot still has a batch in flight: cf_batch_wait first");
+        beginUpload(bt);
         uploadBytes(bt, seq, off, seeds, nReads, paired, static_cast<hipStream_t>(streamv));
     });
 }

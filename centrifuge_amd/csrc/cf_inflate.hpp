@@ -17,6 +17,9 @@
 // fetches aligned 8-byte words, so the uploaded bytes start on an 8-byte boundary and are followed by kInfPad bytes that are read
 // but not used), a byte is written only below the member's ISIZE, a distance reaches back only over bytes this member has produced.
 #pragma once
+#include <cstring>
+#include <stdexcept>
+
 #include "cf_platform.hpp"
 
 namespace cfamd {
@@ -49,6 +52,29 @@ struct DInflate {
     InfStatus *st;
     uint32_t *blocks;            // per member: the deflate blocks it held (nullptr: not kept; the CPU harness asks)
 };
+
+// ---- the host's part: the table of the whole members in z[0, nBytes), from their headers (the test BgzfImpl::fill applies,
+// cf_bytesource.cpp) and trailers.  Member m's payload lies at inAt + (its place in z), its text goes to textAt + (the ISIZEs in
+// front of it); the caller sees to it that textAt + total fits the table's 32 bits.  out == nullptr: nothing is written, the call
+// yields the count and the total.  -> kInfOk, or kInfHeader with nMembers the number of the member whose header or size is not
+// BGZF's.  Members that claim 2^32 - 65536 bytes of text or more are refused by exception: no batch holds them.
+inline uint32_t bgzf_member_table(const uint8_t *z, uint64_t nBytes, uint64_t inAt, uint64_t textAt, InfMember *out, uint64_t &nMembers, uint64_t &total) {
+    uint64_t at = 0;
+    nMembers = 0; total = 0;
+    for (; at < nBytes; nMembers++) {
+        const uint8_t *h = z + at;
+        bool ok = nBytes - at >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4);
+        const uint64_t xlen = ok ? (uint64_t)(h[10] | (h[11] << 8)) : 0, bsize = ok ? (uint64_t)(h[16] | (h[17] << 8)) + 1 : 0;
+        ok = ok && xlen >= 6 && h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0 && bsize >= 12 + xlen + 8 && bsize <= nBytes - at;
+        uint32_t crc = 0, isize = 0;
+        if (ok) { std::memcpy(&crc, h + bsize - 8, 4); std::memcpy(&isize, h + bsize - 4, 4); ok = isize <= kInfMaxOut; }
+        if (!ok) return kInfHeader;
+        if (out) out[nMembers] = InfMember{(uint32_t)(inAt + at + 12 + xlen), (uint32_t)(bsize - 12 - xlen - 8), (uint32_t)(textAt + total), isize, crc};
+        total += isize; at += bsize;
+        if (total >= 0xffff0000ull) throw std::length_error("the text of a batch holds fewer than 2^32 - 65536 bytes (32-bit places in it)");
+    }
+    return kInfOk;
+}
 
 CF_DEV uint64_t inf_load8(const uint8_t *base, uint64_t off) {
     const uint64_t a = off & ~7ull;

@@ -137,6 +137,13 @@ uint64_t emu_inflate(const uint8_t *comp, uint64_t nComp, const uint32_t *member
     return st.bad;
 }
 
+// the member table the host makes of a BGZF upload (bgzf_member_table); out: five words per member, or nullptr for the count and
+// the total alone.  -> kInfOk or kInfHeader (*nMembers: the member refused); ~0: refused by exception (the 32-bit total)
+uint32_t emu_bgzf_member_table(const uint8_t *z, uint64_t nBytes, uint64_t inAt, uint64_t textAt, uint32_t *out, uint64_t *nMembers, uint64_t *total) {
+    try { return bgzf_member_table(z, nBytes, inAt, textAt, reinterpret_cast<InfMember *>(out), *nMembers, *total); }
+    catch (const std::length_error &) { return ~0u; }
+}
+
 // the cut of a BGZF upload's text (text_cut_body) over the markers a plain scan finds; ~0: a marker the body must not have read
 uint64_t emu_text_cut(const uint8_t *text, uint64_t n, uint32_t fastq, uint32_t last, uint64_t posCap, uint64_t *nMarkers) {
     std::vector<uint32_t> pos;

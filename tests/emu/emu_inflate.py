@@ -41,6 +41,8 @@ def lib(wave64=False):
         L.emu_inflate.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.emu_text_cut.restype = C.c_uint64
         L.emu_text_cut.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.emu_bgzf_member_table.restype = C.c_uint32
+        L.emu_bgzf_member_table.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.emu_inflate_wave_lanes.restype = C.c_int
         L.emu_inflate_table_bytes.restype = C.c_uint32
         assert L.emu_inflate_wave_lanes() == (64 if wave64 else 1)
@@ -75,6 +77,30 @@ def member_table(blob):
         at += bsize
         out += isize
     return np.array(rows, dtype=np.uint32).reshape(-1, 5), out
+
+
+HEADER = 16                       # kInfHeader: a member whose gzip header or size is not BGZF's
+
+
+def host_member_table(blob, in_at=0, text_at=0):
+    """the library's own table of the members (bgzf_member_table of cf_inflate.hpp, which the uploads use), made as they make it: a
+    call for the count and the total, one for the table -> table, total, status (OK, or HEADER), the member refused or None;
+    OverflowError: refused by exception (members that claim 2^32 - 65536 bytes of text or more)"""
+    L = lib()
+    blob = bytes(blob)
+    n, total = C.c_uint64(0), C.c_uint64(0)
+    table = None
+    for fill in (False, True):
+        if fill:
+            table = np.full((n.value + 1, 5), 0xA5A5A5A5, dtype=np.uint32)          # (a guard row behind the members')
+            counted = (n.value, total.value)
+        st = L.emu_bgzf_member_table(blob, len(blob), in_at, text_at, table.ctypes.data if fill else None, C.byref(n), C.byref(total))
+        if st == 0xffffffff:
+            raise OverflowError("the members' text does not fit the 32-bit places of a batch")
+        if st:
+            return None, None, st, n.value
+    assert (n.value, total.value) == counted and (table[-1] == 0xA5A5A5A5).all(), "the two calls disagree, or the table was overrun"
+    return table[:-1], total.value, OK, None
 
 
 def inflate(blob, table, n_out, wave64=False, blocks=None):

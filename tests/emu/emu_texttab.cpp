@@ -137,7 +137,7 @@ uint32_t emu_tab_parse(const EmuTabIn *in) {
                      in->idOff, in->idLen, &st, in->textBase, in->stride, in->mate, in->qualOff, in->trim5, in->trim3, in->skip};
     emuThreads((uint64_t)in->recCap + 70, [&](uint32_t r) { text_record_body(d, r); });
     uint32_t flags = st.flags;
-    const bool pairs = text_tab_kind(flags);                           // (what uploadText does with the status)
+    const bool pairs = text_tab_kind(flags);                           // (what uploadTextBlocks does with the status)
     in->status[0] += st.words(); in->status[1] += st.bases(); in->status[2] = st.maxLen > in->status[2] ? st.maxLen : in->status[2]; in->status[3] |= flags;
     in->status[4] = pairs ? 1 : 0;
     if (flags) return 0;

@@ -87,7 +87,7 @@ def upload(blocks, fmt, trim5=0, trim3=0, skip=0, max_reads=0, seed=0, wave64=Fa
     if flags:
         return flags, None
     assert len(set(n_rec)) == 1, "the blocks of mates hold different numbers of records"
-    nq = n_rec[0] - min(n_rec[0], skip)                       # (cf_device.hip uploadText: the skip first, then max_reads)
+    nq = n_rec[0] - min(n_rec[0], skip)                       # (cf_device.hip uploadTextBlocks: the skip first, then max_reads)
     if max_reads and nq > max_reads:
         nq = max_reads
     n = nq * stride

@@ -41,7 +41,7 @@ def plain(fastq):
         t1, t2 = mates(fastq)
         clf, slot = slot_for()
         info = slot.submit_text(t1, capi.TEXT_FASTQ if fastq else capi.TEXT_FASTA, text2=t2)
-        assert not info.irregular
+        assert not info.irregular and info.paired == 1
         _plain[fastq] = (t1, t2, (info.n_reads, info.n_bases, info.max_len), slot.wait_text()[0])
         slot.close(); clf.close()
     return _plain[fastq]
@@ -64,7 +64,7 @@ def through_pair(t1, t2, fmt, size, run1, run2):
         tail1, tail2, info, z1, z2 = slot.submit_bgzf_pair(b"".join(a), b"".join(b), fmt, head1=tail1, head2=tail2, last1=last1, last2=last2)
         assert tail1 is not None and not info.irregular and not z1.corrupt and not z2.corrupt, (calls, info.irregular, z1.corrupt, z2.corrupt)
         inflated[0] += z1.inflated_bytes; inflated[1] += z2.inflated_bytes
-        assert info.n_reads % 2 == 0
+        assert info.n_reads % 2 == 0 and info.paired == 1
         n_reads += info.n_reads; n_bases += info.n_bases; max_len = max(max_len, info.max_len)
         text = slot.wait_text()[0]
         if info.n_reads:
@@ -97,18 +97,18 @@ def test_members_of_the_first_file_only_and_max_reads():
     # no member of the second file yet: no pair is whole, the first file's text comes back as its tail
     some = t1[:t1.index(b">", 20000)]
     tail1, tail2, i, z1, z2 = slot.submit_bgzf_pair(b"".join(members_of(some, 700)), b"", capi.TEXT_FASTA)
-    assert i.n_reads == 0 and not i.irregular and (tail1, tail2) == (some, b"") and z1.inflated_bytes == len(some) and z2.inflated_bytes == 0
+    assert i.n_reads == 0 and not i.irregular and i.paired == 1 and (tail1, tail2) == (some, b"") and z1.inflated_bytes == len(some) and z2.inflated_bytes == 0
     slot.wait_text()
     # ... and goes in as the next call's head, with the rest of both files
     rest = b"".join(members_of(t1[len(some):], 700))
     tail1, tail2, i, z1, z2 = slot.submit_bgzf_pair(rest, b"".join(members_of(t2, 65280)), capi.TEXT_FASTA, head1=tail1, last1=True, last2=True)
-    assert (i.n_reads, i.n_bases, i.max_len) == info and (tail1, tail2) == (b"", b"")
+    assert (i.n_reads, i.n_bases, i.max_len) == info and i.paired == 1 and (tail1, tail2) == (b"", b"")
     assert slot.wait_text()[0] == rows
     # max_reads counts pairs and ends inside the run
     want = slot.submit_text(t1, capi.TEXT_FASTA, text2=t2, max_reads=37)
     want_rows = slot.wait_text()[0]
     tail1, tail2, i, z1, z2 = slot.submit_bgzf_pair(b"".join(members_of(t1, 700)), b"".join(members_of(t2, 700)), capi.TEXT_FASTA, last1=True, last2=True, max_reads=37)
-    assert i.n_reads == 74 == want.n_reads and (tail1, tail2) == (b"", b"")
+    assert i.n_reads == 74 == want.n_reads and i.paired == 1 == want.paired and (tail1, tail2) == (b"", b"")
     assert slot.wait_text()[0] == want_rows and rows.startswith(want_rows)
     slot.close(); clf.close()
 
@@ -124,7 +124,7 @@ def test_refusals_leave_no_batch_and_a_usable_slot():
     assert tail1 is None and tail2 is None and i.irregular & 2048 and not z1.corrupt and not z2.corrupt
     # ... with more to follow in the second file, the first one's three records are its tail
     tail1, tail2, i, z1, z2 = slot.submit_bgzf_pair(m1, b"".join(members_of(short, 700)), capi.TEXT_FASTA, last1=True, last2=False)
-    assert not i.irregular and i.n_reads == 2 * (t2.count(b">") - 4) and tail1.count(b">") == 4 and tail2.count(b">") == 1 and t1.endswith(tail1)
+    assert not i.irregular and i.paired == 1 and i.n_reads == 2 * (t2.count(b">") - 4) and tail1.count(b">") == 4 and tail2.count(b">") == 1 and t1.endswith(tail1)
     slot.wait_text()
     # the first file brings 1.2 MB more text than the second in one call: more than the room its tail has (CF_TEXT_TAIL_ROOM)
     big = t1 * 20
@@ -141,6 +141,6 @@ def test_refusals_leave_no_batch_and_a_usable_slot():
     assert tail1 is None and (z1.corrupt, z2.corrupt, z2.bad_member) == (0, 16, 1)
     # the slot still works
     tail1, tail2, i, z1, z2 = slot.submit_bgzf_pair(m1, b"".join(members_of(t2, 65280)), capi.TEXT_FASTA, last1=True, last2=True)
-    assert (tail1, tail2) == (b"", b"") and (i.n_reads, i.n_bases, i.max_len) == info
+    assert (tail1, tail2) == (b"", b"") and (i.n_reads, i.n_bases, i.max_len) == info and i.paired == 1
     assert slot.wait_text()[0] == rows
     slot.close(); clf.close()

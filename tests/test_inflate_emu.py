@@ -230,3 +230,80 @@ def test_cut_rule():
                 assert k == sum(1 for ch in t[:cut] if ch == marker)
     # more markers than are kept: nothing is cut (the record pass refuses such a block)
     assert E.text_cut(fq, 1, 0, pos_cap=5)[0] == len(fq)
+
+
+# ---- the member table the host makes of an upload's members (bgzf_member_table: the only reader of BGZF headers on the upload path)
+def blob_of(text, size):
+    return b"".join(E.bgzf_member(text[i:i + size]) for i in range(0, len(text), size)) + E.bgzf_member(b"")     # (the empty member a BGZF file ends with)
+
+
+def wide_member(text):
+    """a member with XLEN 12: the BC subfield first, six bytes of another subfield behind it"""
+    co = zlib.compressobj(6, zlib.DEFLATED, -15)
+    payload = co.compress(text) + co.flush()
+    head = b"\x1f\x8b\x08\x04" + bytes(4) + b"\x00\xff" + struct.pack("<H", 12) + b"BC" + struct.pack("<HH", 2, 12 + 12 + len(payload) + 8 - 1) + b"XY\x02\x00\x07\x09"
+    return head + payload + struct.pack("<II", zlib.crc32(text) & 0xffffffff, len(text))
+
+
+TABLE_BLOBS = {
+    "no_member": b"",
+    "one_empty_member": E.bgzf_member(b""),
+    "members_of_700": blob_of(TEXT, 700),
+    "members_of_65280": blob_of(fastq_text(150000, 2), 65280),
+    "xlen_12": wide_member(TEXT[:900]) + E.bgzf_member(TEXT[900:1000]) + wide_member(b""),
+}
+
+
+@pytest.mark.parametrize("in_at,text_at", [(0, 0), (4104, 1000003)])
+@pytest.mark.parametrize("name", sorted(TABLE_BLOBS))
+def test_member_table_of_well_formed_members(name, in_at, text_at):
+    blob = TABLE_BLOBS[name]
+    want, want_total = E.member_table(blob)
+    want = want.astype(np.uint64)
+    want[:, 0] += in_at; want[:, 2] += text_at
+    table, total, status, bad = E.host_member_table(blob, in_at, text_at)
+    assert (status, bad) == (E.OK, None) and total == want_total
+    assert table.shape == want.shape and np.array_equal(table, want)
+    if name == "xlen_12":
+        assert table[0, 0] == in_at + 24 and len(table) == 3
+
+
+def altered(at, value):
+    def f(m):
+        m = bytearray(m); m[at] = value
+        return bytes(m)
+    return f
+
+
+GOOD = E.bgzf_member(b">r\nACGT\n")
+REFUSED = {                                                # what is done to the second of three members
+    "fewer_than_18_bytes_left": lambda m: m[:17],          # (nothing follows it: the blob ends inside the header)
+    "magic_first_byte": altered(0, 0x1e), "magic_second_byte": altered(1, 0x8a),
+    "cm_not_8": altered(2, 9), "fextra_clear": altered(3, 0),
+    "xlen_below_6": altered(10, 5),
+    "no_B": altered(12, ord("X")), "no_C": altered(13, ord("X")), "slen_low": altered(14, 3), "slen_high": altered(15, 1),
+    "bsize_below_header_and_trailer": lambda m: m[:16] + struct.pack("<H", 12 + 6 + 8 - 2) + m[18:],
+    "bsize_beyond_the_bytes_given": lambda m: m[:16] + struct.pack("<H", 0xffff) + m[18:],
+    "isize_65537": lambda m: m[:-4] + struct.pack("<I", 65537),
+}
+
+
+@pytest.mark.parametrize("name", sorted(REFUSED))
+def test_member_table_refuses_a_header_that_is_not_bgzfs(name):
+    assert E.host_member_table(GOOD * 3)[2:] == (E.OK, None)
+    second = REFUSED[name](GOOD)
+    blob = GOOD + second + (GOOD if len(second) == len(GOOD) else b"")
+    assert 3 * len(GOOD) < 0xffff
+    assert E.host_member_table(blob, 8, 64)[2:] == (E.HEADER, 1)
+    assert E.host_member_table(second + GOOD)[2:] == (E.HEADER, 0)
+
+
+def test_member_table_refuses_a_text_beyond_the_32_bit_places():
+    """ISIZE trailers that sum to 2^32 - 65536 or more: refused by exception from the trailers alone (members that claim 64 KiB each)"""
+    big = E.bgzf_member(b"")[:-4] + struct.pack("<I", 65536)
+    with pytest.raises(OverflowError):
+        E.host_member_table(big * 65540)
+    with pytest.raises(OverflowError):
+        E.host_member_table(big * 65535)                   # 2^32 - 65536 itself
+    table, total, status, bad = E.host_member_table(big * 65534)
+    assert status == E.OK and total == 65534 * 65536 and int(table[-1, 2]) + 65536 == total
