@@ -199,7 +199,7 @@ EXPORTS = [
     "cf_kreport_enable", "cf_kreport_reset", "cf_kreport_get", "cf_kreport_write", "cf_batch_kreport_ms", "cf_batch_text_names",
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
-    "cf_debug_prim_scan",
+    "cf_debug_prim_scan", "cf_debug_inflate", "cf_debug_deflate",
 ]
 
 _lib = None
@@ -305,6 +305,8 @@ def lib():
         "cf_build_taxonomy": (i32, [C.POINTER(BuildInput), cp, C.c_char_p, u64]),
         "cf_build_describe": (i32, [C.POINTER(BuildInput), cp, C.c_char_p, u64]),
         "cf_debug_prim_scan": (i32, [i32, i32, i32, vp, u64, vp]),
+        "cf_debug_inflate": (i32, [i32, i32, cp, u64, u64, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int64)]),
+        "cf_debug_deflate": (i32, [i32, cp, u64, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1009,6 +1011,36 @@ def prim_scan(x, inclusive=False, device=0):
     if st != 0:
         raise CfError("%s: %s" % (L.cf_strerror(st).decode(), L.cf_build_last_error().decode()))
     return out
+
+
+def debug_inflate(members, by_lane=False, device=0):
+    """Whole BGZF members through the device inflater on its own (cf_debug_inflate), a wavefront or — by_lane — a lane per member
+    -> text (0x5A where nothing was written), status (a word per member, 0: not corrupt), blocks (the deflate blocks read per
+    member), the first corrupt member or None.  CfError: a header that is not BGZF's, or a margin around a device buffer changed."""
+    members = bytes(members)
+    n_members, n_text, at = 0, 0, 0
+    while at + 18 <= len(members):                # (room for the outputs from the sizes the members name; the library checks them)
+        bsize = int.from_bytes(members[at + 16:at + 18], "little") + 1
+        n_text += int.from_bytes(members[at + bsize - 4:at + bsize], "little") if at + bsize <= len(members) else 0
+        n_members += 1
+        at += bsize
+    text = np.zeros(n_text + 1, dtype=np.uint8)
+    status, blocks = np.zeros(n_members + 1, dtype=np.uint32), np.zeros(n_members + 1, dtype=np.uint32)
+    nm, nt, bad = C.c_uint64(0), C.c_uint64(0), C.c_int64(-1)
+    _check(lib().cf_debug_inflate(device, int(by_lane), members, len(members), n_members, n_text, text.ctypes.data, status.ctypes.data,
+                                  blocks.ctypes.data, C.byref(nm), C.byref(nt), C.byref(bad)))
+    return text[:nt.value].tobytes(), status[:nm.value].copy(), blocks[:nm.value].copy(), (None if bad.value < 0 else bad.value)
+
+
+def debug_deflate(text, member=65280, device=0):
+    """Text through the device deflater on its own (cf_debug_deflate) -> the BGZF members one behind the other (bytes), their sizes"""
+    text = bytes(text)
+    n_members = (len(text) + member - 1) // member if member else 0
+    out = np.zeros(n_members * ((member + 31 + 7) & ~7) + 1, dtype=np.uint8)
+    sizes = np.zeros(n_members + 1, dtype=np.uint32)
+    n, nm = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().cf_debug_deflate(device, text, len(text), member, out.ctypes.data, out.size - 1, C.byref(n), sizes.ctypes.data, n_members, C.byref(nm)))
+    return out[:n.value].tobytes(), sizes[:nm.value].copy()
 
 
 class Report:

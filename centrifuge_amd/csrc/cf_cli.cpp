@@ -1863,7 +1863,9 @@ int run(int argc, const char **argv) {
                         if (nMem && bytes + bs + is > budget) break;
                         bytes += bs + is; end[f] += bs; cum[f] += is; nMem++;
                     }
-                    if (!nMem) break;
+                    // (a run that ends at bytes that are no member is the parser pool's whole, as a run with a corrupt member is: the
+                    // host readers meet those bytes in the block that holds the run's reads, and print none of them)
+                    if (!nMem || badHeader) break;
                     budget = std::min<size_t>(kBlock, budget * 2);
                     std::unique_ptr<Batch> b = textBatch(true);
                     b->tBgzf = true; b->tMembers = nMem; b->tIdx = idx++; b->tFirst = pos[0] == 0 && pos[1] == 0;
@@ -1930,7 +1932,7 @@ int run(int argc, const char **argv) {
                         if (nMem && bytes + bs + is > kBlock) break;
                         bytes += bs + is; end += bs; nMem++;
                     }
-                    if (!nMem) break;
+                    if (!nMem || badHeader) break;          // (as for mates: the run in front of bytes that are no member goes with them)
                     std::unique_ptr<Batch> b = textBatch(false);
                     b->tBgzf = true; b->tMembers = nMem; b->tFd = fd; b->tOff = pos; b->tLen = end - pos; b->tFirst = pos == 0; b->tLast = end == fsize; b->tIdx = idx++; b->tPath = &in.f1;
                     pos = end;

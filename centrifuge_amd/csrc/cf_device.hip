@@ -2087,6 +2087,13 @@ static void uploadDense(cf_batch *bt, const cf_dense_reads *in, hipStream_t st) 
 //                    parse.
 // A block that is not in the plain form leaves the slot without a batch (info->irregular says why): the caller's host parser takes
 // it.  So do a member that is corrupt (zi->corrupt) and a tail beyond its room.
+// Queued on st: the members of d inflated (cf_inflate.hpp), a wavefront per member or — byLane — a lane per member.  The members'
+// bytes lie in a room of inflateInRoom(their bytes): the inflater fetches aligned 8-byte words, kInfPad bytes behind the last one at most.
+static uint64_t inflateInRoom(uint64_t inBytes) { return inBytes + kInfPad + 8; }
+static void enqueueInflate(const DInflate &d, bool byLane, hipStream_t st) {
+    if (byLane) hipLaunchKernelGGL(k_inflate_lane, dim3((unsigned)((d.nMembers + 63) / 64)), dim3(64), 0, st, d);
+    else hipLaunchKernelGGL(k_inflate, dim3((unsigned)((d.nMembers + 256 / CF_WAVE - 1) / (256 / CF_WAVE))), dim3(256), 0, st, d);
+}
 struct TextSource { const void *head; uint64_t headBytes; const void *members; uint64_t memberBytes; bool last; cf_bgzf_info *zi; };
 constexpr uint64_t kBgzfTailRoom = 1u << 20;
 static const char *const kTextTooLong = "the texts of a batch hold fewer than 2^32 - 65536 bytes (32-bit places in them)";
@@ -2130,7 +2137,7 @@ static void uploadTextBlocks(cf_batch *bt, uint32_t format, uint32_t globalSeed,
     bt->txSt.ensure(1); bt->hTxSt.ensure(1); bt->hTxTotal.ensure(2);
     HIP_OK(hipMemsetAsync(bt->txSt.p, 0, sizeof(TextStatus), st));
     if (cutting) {                                         // zCut / hZCut: per block its cut and the markers in front of it; hZCut + 4: the inflater's status
-        bt->zIn.ensure(inBytes + kInfPad + 8); bt->zMembers.ensure(nMembers + 1); bt->zErr.ensure(nMembers + 1); bt->zSt.ensure(1); bt->zCut.ensure(4);
+        bt->zIn.ensure(inflateInRoom(inBytes)); bt->zMembers.ensure(nMembers + 1); bt->zErr.ensure(nMembers + 1); bt->zSt.ensure(1); bt->zCut.ensure(4);
         bt->hZMembers.ensure(nMembers + 1); bt->hZCut.ensure(6); bt->hTail.ensure(kBgzfTailRoom + 16);
         if (nBlocks == 2) bt->hTail2.ensure(kBgzfTailRoom + 16);
         for (int k = 0; k < nBlocks; k++) { uint64_t inflated; (void)memberTable(k, at[k] + src[k].headBytes, bt->hZMembers.p + (k ? nM[0] : 0), nM[k], inflated); }
@@ -2144,10 +2151,8 @@ static void uploadTextBlocks(cf_batch *bt, uint32_t format, uint32_t globalSeed,
     }
     if (nMembers) {
         HIP_OK(hipMemcpyAsync(bt->zMembers.p, bt->hZMembers.p, nMembers * sizeof(InfMember), hipMemcpyHostToDevice, st));
-        const DInflate d{bt->zIn.p, bt->zMembers.p, (uint32_t)nMembers, bt->text.p, bt->zErr.p, bt->zSt.p, nullptr};
         static const bool byLane = cfamd::cf_knob("CF_INFLATE_LANES") && std::atoi(cfamd::cf_knob("CF_INFLATE_LANES")) == 1;
-        if (byLane && nBlocks == 1) hipLaunchKernelGGL(k_inflate_lane, dim3((unsigned)((nMembers + 63) / 64)), dim3(64), 0, st, d);     // (the knob is the single-file entry's: cf_knobs.hpp)
-        else hipLaunchKernelGGL(k_inflate, dim3((unsigned)((nMembers + 256 / CF_WAVE - 1) / (256 / CF_WAVE))), dim3(256), 0, st, d);
+        enqueueInflate(DInflate{bt->zIn.p, bt->zMembers.p, (uint32_t)nMembers, bt->text.p, bt->zErr.p, bt->zSt.p, nullptr}, byLane && nBlocks == 1, st);     // (the knob is the single-file entry's: cf_knobs.hpp)
     }
     const dim3 bl(256);
     const uint32_t seed0 = (globalSeed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
@@ -3334,6 +3339,112 @@ cf_status cf_debug_scan(int device, int mode, const uint32_t *in, uint64_t n, ui
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpy(sums, da.p, (n + 1) * 8, hipMemcpyDeviceToHost));
         if (mode == SCAN_HITS) HIP_OK(hipMemcpy(counts, dc.p, (n + 1) * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// The codec's kernels on their own.  Every device buffer a kernel writes to or reads bytes from lies between margins of kTapMargin
+// bytes filled with kTapFill; a margin byte that has changed after the run is an error of the tap's own.
+constexpr uint64_t kTapMargin = 256;
+constexpr uint8_t kTapFill = 0xA5, kTapUnwritten = 0x5A;
+struct TapBuf {
+    DevBuf<uint8_t> buf;
+    uint64_t room = 0;
+    uint8_t *p = nullptr;                    // the room between the margins (256-byte aligned, as hipMalloc's memory is)
+    void make(uint64_t bytes, uint8_t fill) {
+        room = bytes;
+        buf.alloc(kTapMargin + room + kTapMargin);
+        p = buf.p + kTapMargin;
+        HIP_OK(hipMemset(buf.p, kTapFill, kTapMargin + room + kTapMargin));
+        if (room) HIP_OK(hipMemset(p, fill, room));
+    }
+    void check(const char *what) const {
+        uint8_t m[2 * kTapMargin];
+        HIP_OK(hipMemcpy(m, buf.p, kTapMargin, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(m + kTapMargin, p + room, kTapMargin, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < 2 * kTapMargin; i++)
+            if (m[i] != kTapFill) throw std::runtime_error(std::string("a byte of the margin ") + (i < kTapMargin ? "in front of " : "behind ") + what + " was changed");
+    }
+};
+
+// Whole BGZF members through the upload's inflater: its member table, its room behind the members, its launch (enqueueInflate).
+cf_status cf_debug_inflate(int device, int by_lane, const void *members, uint64_t n_bytes, uint64_t member_cap, uint64_t text_cap,
+                           uint8_t *text, uint32_t *status, uint32_t *blocks, uint64_t *n_members, uint64_t *text_bytes, int64_t *bad_member) {
+    if ((!members && n_bytes) || !text || !status || !blocks || !n_members || !text_bytes || !bad_member) return CF_ERR_ARG;
+    if (!haveDevice()) return CF_ERR_NO_DEVICE;
+    return guard([&] {
+        HIP_OK(hipSetDevice(device));
+        const uint8_t *z = static_cast<const uint8_t *>(members);
+        uint64_t nM = 0, total = 0;
+        if (n_bytes >= 0xffff0000ull) throw ArgError("cf_debug_inflate: the members hold fewer than 2^32 - 65536 bytes");
+        if (bgzf_member_table(z, n_bytes, 0, 0, nullptr, nM, total) != kInfOk) throw ArgError("cf_debug_inflate: member " + std::to_string(nM) + " has no BGZF header");
+        *n_members = nM; *text_bytes = total; *bad_member = -1;
+        if (nM > member_cap || total > text_cap) throw ArgError("cf_debug_inflate: the output arrays are too small");
+        if (!nM) return;
+        std::vector<InfMember> table(nM);
+        (void)bgzf_member_table(z, n_bytes, 0, 0, table.data(), nM, total);
+        TapBuf in, out;
+        in.make(n_bytes, 0);
+        out.make(total, kTapUnwritten);
+        if (kTapMargin < inflateInRoom(0)) throw std::logic_error("the margin is the inflater's room behind the members");
+        DevBuf<InfMember> dm; DevBuf<uint32_t> err, blk; DevBuf<InfStatus> st;
+        dm.upload(table); err.alloc(nM + 1); blk.alloc(nM + 1); st.alloc(1);
+        HIP_OK(hipMemcpy(in.p, z, n_bytes, hipMemcpyHostToDevice));
+        HIP_OK(hipMemset(st.p, 0, sizeof(InfStatus)));
+        HIP_OK(hipMemset(err.p, 0xff, (nM + 1) * 4)); HIP_OK(hipMemset(blk.p, 0xff, (nM + 1) * 4));
+        enqueueInflate(DInflate{in.p, dm.p, (uint32_t)nM, out.p, err.p, st.p, blk.p}, by_lane != 0, nullptr);
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipGetLastError());
+        in.check("the members"); out.check("the text");
+        std::vector<uint8_t> back(n_bytes);
+        HIP_OK(hipMemcpy(back.data(), in.p, n_bytes, hipMemcpyDeviceToHost));
+        if (std::memcmp(back.data(), z, n_bytes) != 0) throw std::runtime_error("a byte of the members was changed");
+        InfStatus hs;
+        HIP_OK(hipMemcpy(&hs, st.p, sizeof hs, hipMemcpyDeviceToHost));
+        if (hs.bad) *bad_member = (int64_t)(0xffffffffu - hs.bad);
+        if (total) HIP_OK(hipMemcpy(text, out.p, total, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(status, err.p, nM * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(blocks, blk.p, nM * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// Text through the deflater of cf_batch_wait_text_bgzf (enqueueDeflate): the members at their stride, their sizes summed, the
+// members moved together into the room the text lay in.
+cf_status cf_debug_deflate(int device, const void *text, uint64_t n_bytes, uint32_t member, uint8_t *out, uint64_t out_cap,
+                           uint64_t *out_bytes, uint32_t *sizes, uint64_t sizes_cap, uint64_t *n_members) {
+    if ((!text && n_bytes) || !out || !out_bytes || !sizes || !n_members) return CF_ERR_ARG;
+    if (!def_member_ok(member)) { g_err = "cf_debug_deflate: a member holds a multiple of 64 bytes of text, from 64 to 65280"; return CF_ERR_ARG; }
+    if (!haveDevice()) return CF_ERR_NO_DEVICE;
+    return guard([&] {
+        HIP_OK(hipSetDevice(device));
+        const uint64_t nM = (n_bytes + member - 1) / member, zBytes = nM * def_stride(member);
+        *n_members = nM; *out_bytes = 0;
+        if (nM > sizes_cap || zBytes > out_cap) throw ArgError("cf_debug_deflate: the output arrays are too small (a member takes up to its text + 31 bytes, rounded up to 8)");
+        if (!nM) return;
+        if (nM > 0xffffffffull) throw ArgError("cf_debug_deflate: too many members");
+        TapBuf tx, z;
+        tx.make(std::max<uint64_t>(n_bytes + kInfPad, zBytes), 0);
+        z.make(zBytes, kTapUnwritten);
+        DevBuf<uint32_t> zSize, tileC; DevBuf<uint64_t> zOff, tileA;
+        zSize.alloc(nM + 16); zOff.alloc(nM + 16); tileA.alloc(scan_tiles_for(nM) + 1); tileC.alloc(scan_tiles_for(nM) + 1);
+        PinBuf<uint64_t> hTotal; hTotal.ensure(1);
+        HIP_OK(hipMemcpy(tx.p, text, n_bytes, hipMemcpyHostToDevice));
+        enqueueDeflate(tx.p, n_bytes, member, nM, z.p, zSize.p, zOff.p, tileA.p, tileC.p, hTotal.p, nullptr, nullptr);
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipGetLastError());
+        tx.check("the text"); z.check("the members");
+        const uint64_t total = *hTotal.p;
+        if (total > zBytes) throw std::logic_error("the BGZF members outgrew their room");
+        *out_bytes = total;
+        HIP_OK(hipMemcpy(out, tx.p, total, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(sizes, zSize.p, nM * 4, hipMemcpyDeviceToHost));
+        // (a member's room behind its last byte is as it was)
+        std::vector<uint8_t> rooms(zBytes);
+        HIP_OK(hipMemcpy(rooms.data(), z.p, zBytes, hipMemcpyDeviceToHost));
+        for (uint64_t m = 0; m < nM; m++) {
+            if (sizes[m] > def_stride(member)) throw std::logic_error("a BGZF member outgrew its room");
+            for (uint64_t i = sizes[m]; i < def_stride(member); i++)
+                if (rooms[m * def_stride(member) + i] != kTapUnwritten) throw std::runtime_error("a byte behind member " + std::to_string(m) + " in its room was changed");
+        }
     });
 }
 

@@ -701,6 +701,18 @@ cf_status cf_debug_rank1(cf_index *, const uint8_t *chars, const uint64_t *rows,
 /* the prefix sums of a batch on their own: n u32 items -> n + 1 exclusive sums of ceil(x/32) (mode 0), x (mode 1) or 2x
  * plus the exclusive counts of non-zero items (mode 2) */
 cf_status cf_debug_scan(int device, int mode, const uint32_t *in, uint64_t n, uint64_t *sums, uint32_t *counts);
+/* The device DEFLATE codec on its own, through the host helpers and kernels the uploads and cf_batch_wait_text_bgzf use.  Every
+ * device buffer lies between filled margins of 256 bytes; a margin byte that has changed fails the call (cf_last_error names the margin).
+ * cf_debug_inflate: whole BGZF members (n_bytes of them; a header that is not BGZF's is CF_ERR_ARG) inflated by a wavefront per
+ * member, or — by_lane — by a lane per member.  text: the ISIZEs' sum (*text_bytes <= text_cap), 0x5A where nothing was written;
+ * status / blocks: per member (*n_members <= member_cap) why it is corrupt (0: it is not) and the deflate blocks read;
+ * *bad_member: the first corrupt member, -1: none.
+ * cf_debug_deflate: text as BGZF members of `member` text bytes (a multiple of 64, 64 .. 65280) -> the members one behind the
+ * other in out (*out_bytes; out_cap: ((member + 31 + 7) & ~7) per member), sizes: their bytes (*n_members <= sizes_cap). */
+cf_status cf_debug_inflate(int device, int by_lane, const void *members, uint64_t n_bytes, uint64_t member_cap, uint64_t text_cap,
+                           uint8_t *text, uint32_t *status, uint32_t *blocks, uint64_t *n_members, uint64_t *text_bytes, int64_t *bad_member);
+cf_status cf_debug_deflate(int device, const void *text, uint64_t n_bytes, uint32_t member, uint8_t *out, uint64_t out_cap,
+                           uint64_t *out_bytes, uint32_t *sizes, uint64_t sizes_cap, uint64_t *n_members);
 /* random 128-byte-side read bandwidth of the device over the resident sides
  * (the roofline denominator of SURVEY.md §8d): GB/s over `n_loads` loads. */
 cf_status cf_debug_random_read_gbps(cf_index *, uint64_t n_loads, int dependent_steps, double *gbps);

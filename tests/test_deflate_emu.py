@@ -11,12 +11,14 @@ import zlib
 import numpy as np
 import pytest
 
+import codeccases as K
 import common
 from emu import emu_deflate as D
 from emu import emu_inflate as I
 
 EOF = D.EOF_MEMBER
-PIECE = D.MEMBER // 64
+PIECE = K.PIECE
+assert K.MEMBER == D.MEMBER
 
 
 def check(text, member=D.MEMBER):
@@ -65,12 +67,15 @@ def test_empty_text_gives_no_member():
     assert blob == b"" and len(sizes) == 0
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 4, PIECE - 1, PIECE, PIECE + 1, D.MEMBER - 1, D.MEMBER, D.MEMBER + 1])
+def test_the_tables_sizes_are_the_edges():
+    assert K.EDGE_SIZES == [1, 2, 3, 4, PIECE - 1, PIECE, PIECE + 1, D.MEMBER - 1, D.MEMBER, D.MEMBER + 1]
+    assert K.ONE_BYTE_RUNS == [3, 257, 258, 259, 260, PIECE, PIECE + 2, 3 * PIECE + 7, D.MEMBER, D.MEMBER + 300]
+    assert K.PERIODS == [1, 2, 52, 500, 13056, 13057]
+
+
+@pytest.mark.parametrize("n", K.EDGE_SIZES)
 def test_sizes_at_the_edges_of_a_piece_and_of_a_member(n):
-    rng = np.random.default_rng(n)
-    words = [b"seq%d\t" % i for i in range(40)] + [b"\n", b"100\t", b"genus\t"]
-    text = b"".join(words[int(k)] for k in rng.integers(0, len(words), n // 3 + 2))[:n]
-    assert len(text) == n
+    text = K.rows_text(n)
     blob, sizes = check(text)
     assert len(sizes) == (2 if n > D.MEMBER else 1)
     if n == D.MEMBER + 1:
@@ -102,51 +107,53 @@ def test_golden_tsv_in_dozens_of_members(which):
         assert len(check(text)[0]) < len(text)            # ... at the default member size too
 
 
-@pytest.mark.parametrize("n", [3, 257, 258, 259, 260, PIECE, PIECE + 2, 3 * PIECE + 7, D.MEMBER, D.MEMBER + 300])
+@pytest.mark.parametrize("n", K.ONE_BYTE_RUNS)
 def test_one_byte_repeated(n):
     """distance 1, matches of 258 that run into the ends of pieces and members"""
     blob, _ = check(b"\0" * n)
     assert len(blob) < n // 16 + 64
 
 
-@pytest.mark.parametrize("n", [1, 2, 52, 500, 13056, 13057])
+@pytest.mark.parametrize("n", K.PERIODS)
 def test_distance_shorter_than_the_match(n):
     check(b"ACGTA" * n)
     check(b"AB" * n + b"A")
 
 
 def test_matches_at_the_very_end_and_across_a_piece_end():
-    # the last three bytes are a match
-    check(b"abcdefgh-xyz-abc")
-    check(b"0123456789" * 7 + b"##" + b"789")
-    # a run that starts in front of a piece's end and goes on behind it: the match is clipped at the end, the next lane starts anew
-    unit = bytes(range(33, 97))
-    for lead in (PIECE - 70, PIECE - 5, PIECE - 3, PIECE - 2, PIECE - 1):
-        text = bytes((7 * i) % 23 + 97 for i in range(lead - 64)) + unit + unit + unit + b"tail"
+    # the last three bytes are a match; a run that starts in front of a piece's end and goes on behind it: the match is clipped at
+    # the end, the next lane starts anew
+    texts = K.match_end_texts()
+    assert len(texts) == 7 and texts[0] == b"abcdefgh-xyz-abc"
+    for text in texts:
         check(text)
     # ... the same at a member's end
-    text = (b"r%d\tgenus\t102\n" % 7) * 5100
-    assert len(text) > D.MEMBER
-    check(text)
+    check(K.member_end_text())
 
 
 def test_nine_bit_literals_mixed_with_ascii():
-    rng = np.random.default_rng(5)
-    hi = rng.integers(144, 256, 3000, dtype=np.uint8).tobytes()
-    text = b"".join(b"read_%d\t" % i + hi[3 * i:3 * i + 3] + b"\tseq7\t1007\n" for i in range(1000))
-    check(text)
-    check(hi)
-    check(hi[:700] + b"plain ascii plain ascii plain ascii" * 30 + hi[700:1500], member=1024)
+    texts = K.nine_bit_texts()
+    assert len(texts) == 3 and texts[1] == (K.high_bytes(), D.MEMBER) and texts[2][1] == 1024
+    for text, member in texts:
+        check(text, member=member)
 
 
 def test_random_bytes_are_stored():
-    text = np.random.default_rng(11).integers(0, 256, D.MEMBER, dtype=np.uint8).tobytes()
+    text = K.random_member()
+    assert len(text) == D.MEMBER
     blob, sizes = check(text)
     assert len(sizes) == 1 and is_stored(blob) and len(blob) == D.MEMBER + 5 + 26
     # names of bytes >= 144 only: 9 bits a literal, stored as well; a member of both kinds of text is not
-    hi = np.random.default_rng(12).integers(144, 256, 4096, dtype=np.uint8).tobytes()
-    blob, sizes = check(hi + b"A" * 4096, member=4096)
+    blob, sizes = check(K.high_then_ascii(), member=4096)
     assert is_stored(blob[:sizes[0]]) and not is_stored(blob[sizes[0]:])
+
+
+def test_the_stored_form_is_taken_only_where_it_is_shorter():
+    """members of 64 random bytes: stored exactly where the literals' fixed block would take more bytes than the text and 5, fixed
+    where the two are equal"""
+    part = K.threshold_text()
+    blob, sizes = check(part, member=64)
+    assert K.stored_where_shorter(part, 64, [is_stored(blob[int(sizes[:m].sum()):]) for m in range(len(sizes))])
 
 
 def test_the_bytes_are_a_function_of_the_text():

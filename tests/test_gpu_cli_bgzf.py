@@ -1,8 +1,8 @@
 """centrifuge-class on BGZF read files: an unpaired .gz file whose members are BGZF's goes up compressed, in runs of whole members,
 is inflated on the device (cf_batch_upload_bgzf) and takes the device text path from there — the same bytes out as the host
 threads give and as the reference's golden TSV and report hold; a file with records outside the plain form is handed to the
-parser pool where they begin.  The files are made here with zlib (raw deflate in BGZF headers).  Corrupt members are the CPU
-harness's (tests/test_inflate_emu.py), never the GPU's."""
+parser pool where they begin.  The files are made here with zlib (raw deflate in BGZF headers).  Corrupt members — in the CPU
+harness (tests/test_inflate_emu.py) and, as damaged files given to this program, on the GPU — are tests/test_gpu_codec.py's."""
 import gzip
 import os
 import re

@@ -1,8 +1,8 @@
 """BGZF members through the batch ABI on the GPU (cf_batch_upload_bgzf: include/centrifuge_amd.h): the read files of synth_small as
 BGZF members made here with zlib — 700 bytes of text each, 65,280 (bgzip's size) and as much as a member takes —, uploaded in runs
 of one, three and all members with the tails handed on; the reads that come out and the rows printed for them are those of the
-plain file through cf_batch_upload_text, and the reference's golden TSV.  Corrupt members are the CPU harness's
-(tests/test_inflate_emu.py), never the GPU's."""
+plain file through cf_batch_upload_text, and the reference's golden TSV.  Corrupt members — in the CPU harness
+(tests/test_inflate_emu.py) and, through this entry and the inflater's tap, on the GPU — are tests/test_gpu_codec.py's."""
 import os
 
 import pytest

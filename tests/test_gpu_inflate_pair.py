@@ -1,8 +1,8 @@
 """The BGZF files of mates through the batch ABI on the GPU (cf_batch_upload_bgzf_pair: include/centrifuge_amd.h): r1.fa / r2.fa of
 synth_small as BGZF members made here with zlib, uploaded in runs whose lengths differ between the two files, the two tails handed
 on; the device cuts both texts of a call behind a common record.  The reads that come out and the rows printed for them are those
-of the plain files through cf_batch_upload_text (text, text2), and the reference's golden TSV.  Corrupt members are the CPU
-harness's (tests/test_inflate_emu.py), never the GPU's."""
+of the plain files through cf_batch_upload_text (text, text2), and the reference's golden TSV.  Corrupt members — in the CPU
+harness (tests/test_inflate_emu.py) and, through this entry and the inflater's tap, on the GPU — are tests/test_gpu_codec.py's."""
 import os
 
 import numpy as np

@@ -4,7 +4,7 @@ synth_small's read files, the last readID lengthened until the text's length is 
 (kTextPiece), and the empty text.  Each text goes up as a plain block, as BGZF members of 64 and of 65,280 bytes of text, as a head
 without members and as a head of 1, 63 and 64 bytes with the rest in members; mates as two plain blocks and as the members of two
 files, with a head alone on either side.  Every way gives the reads, bases, longest read and printed rows of the plain block, and
-leaves no tail.  No corrupt member goes to the GPU: those are the CPU harness's (tests/test_inflate_emu.py)."""
+leaves no tail.  No corrupt member comes here: those are tests/test_gpu_codec.py's, on the GPU as in the CPU harness."""
 import os
 
 import pytest

@@ -2,90 +2,55 @@
 per member and wavefronts of 64 lanes — against zlib, byte for byte: BGZF members made here with zlib's raw deflate (stored, fixed
 and dynamic blocks, every strategy that changes what the stream holds), the sizes and distances at the format's limits, and corrupt
 streams: every check the decoder makes once, and seeded single-byte flips.  A corrupt stream ends in a status, the guard bytes the
-harness puts around the compressed bytes and around the text stay as they are (emu_inflate.inflate asserts it).  The cut rule of a
+harness puts around the compressed bytes and around the text stay as they are (emu_inflate.inflate asserts it).  The streams are
+those of tests/codeccases.py, which tests/test_gpu_codec.py gives to the device as well.  The cut rule of a
 BGZF upload (text_cut_body) is stated here once more in plain Python."""
-import random
 import struct
 import zlib
 
 import numpy as np
 import pytest
 
+import codeccases as K
+from codeccases import CRAFTED, TEXT, fastq_text
 from emu import emu_inflate as E
 
 WAVES = [False, True]
 
 
-def fastq_text(n_bytes, seed):
-    rng = random.Random(seed)
-    out = bytearray()
-    i = 0
-    while len(out) < n_bytes:
-        L = rng.choice([36, 100, 151])
-        out += b"@read%d/1\n%s\n+\n%s\n" % (i, bytes(rng.choice(b"ACGT") for _ in range(L)), bytes(rng.randrange(33, 74) for _ in range(L)))
-        i += 1
-    return bytes(out[:n_bytes])
+def inflate_members(members, wave64, blocks=None):
+    """whole members (bytes each) through the harness -> text, err, bad"""
+    blob = b"".join(members)
+    table, n = E.member_table(blob)
+    return E.inflate(blob, table, n, wave64, blocks)
 
 
 def roundtrip(members_text, wave64, blocks=None, **kw):
-    blob = b"".join(E.bgzf_member(t, **kw) for t in members_text)
-    table, n = E.member_table(blob)
-    out, err, bad = E.inflate(blob, table, n, wave64, blocks)
+    out, err, bad = inflate_members([E.bgzf_member(t, **kw) for t in members_text], wave64, blocks)
     assert bad is None and not err.any(), (bad, err)
     assert out == b"".join(members_text)
-    return blob
-
-
-TEXT = fastq_text(40000, 1)
-STREAMS = {
-    "stored": dict(level=0),
-    "fixed": dict(level=6, strategy=zlib.Z_FIXED),
-    "level1": dict(level=1), "level6": dict(level=6), "level9": dict(level=9),
-    "rle": dict(level=6, strategy=zlib.Z_RLE),
-    "huffman_only": dict(level=6, strategy=zlib.Z_HUFFMAN_ONLY),
-}
 
 
 @pytest.mark.parametrize("wave64", WAVES)
-@pytest.mark.parametrize("name", sorted(STREAMS))
+@pytest.mark.parametrize("name", sorted(K.STREAMS))
 def test_streams(name, wave64):
-    roundtrip([TEXT, TEXT[:777], b"", TEXT[5:6]], wave64, **STREAMS[name])
+    roundtrip(K.STREAM_TEXTS, wave64, **K.STREAMS[name])
 
 
 @pytest.mark.parametrize("wave64", WAVES)
 def test_sizes_and_distances(wave64):
-    rng = random.Random(7)
-    far = bytes(rng.randrange(256) for _ in range(32768))
-    for level in (1, 6, 9):
-        roundtrip([b"", b"A", b"", fastq_text(65536, 3)[:65536]], wave64, level=level)
-        roundtrip([b"G" * 65536], wave64, level=level)                 # distance 1, matches of 258
-        roundtrip([far + far[:300]], wave64, level=level)               # (zlib stores it: the match at that distance is the next test's)
-        roundtrip([b"ACGTA" * 13000], wave64, level=level)              # a distance shorter than the match, no power of two
-    # 65,536 bytes stored (the member is larger than its text: level 0 of a shorter text, for the 64 KiB a BGZF member may take)
-    roundtrip([far + far[:32000]], wave64, level=0)
+    for texts, kw in K.sizes_and_distances():
+        roundtrip(texts, wave64, **kw)
 
 
 @pytest.mark.parametrize("wave64", WAVES)
 def test_a_match_at_the_distance_limit(wave64):
-    """zlib never emits a distance beyond 32,768 - 262 (and stores random bytes), so the stream is written by hand: 32,768 bytes in a
-    stored block, then a fixed block with ONE match — length symbol 285 (258 bytes), distance symbol 29 with its 13 extra bits all
-    set: 24,577 + 8,191 = 32,768, the format's limit and exactly what the member has produced — and the end-of-block code."""
-    rng = random.Random(7)
-    far = bytes(rng.randrange(256) for _ in range(32768))
-    payload = Bits().put(0, 1).put(0, 2).bytes() + struct.pack("<HH", 32768, 32768 ^ 0xffff) + far
-    payload += Bits().put(1, 1).put(1, 2).code(0xc5, 8).code(29, 5).put(8191, 13).code(0, 7).bytes()
-    text = far + far[:258]
+    """codeccases.distance_limit: one match at distance 32,768 behind exactly 32,768 bytes, and behind 32,767"""
+    (payload, text), (short, claimed) = K.distance_limit()
     assert zlib.decompress(payload, -15) == text
-    blob = E.bgzf_member(text, payload=payload)
-    table, n = E.member_table(blob)
-    out, err, bad = E.inflate(blob, table, n, wave64)
+    out, err, bad = inflate_members([E.bgzf_member(text, payload=payload)], wave64)
     assert bad is None and not err.any() and out == text
-    # one byte further back than the member has produced: the same stream behind 32,767 bytes
-    short = Bits().put(0, 1).put(0, 2).bytes() + struct.pack("<HH", 32767, 32767 ^ 0xffff) + far[:32767]
-    short += Bits().put(1, 1).put(1, 2).code(0xc5, 8).code(29, 5).put(8191, 13).code(0, 7).bytes()
-    blob = E.bgzf_member(far[:32767] + bytes(258), payload=short)
-    table, n = E.member_table(blob)
-    out, err, bad = E.inflate(blob, table, n, wave64)
+    out, err, bad = inflate_members([E.bgzf_member(claimed, payload=short)], wave64)
     assert bad == 0 and err[0] == E.DIST_TOO_FAR
 
 
@@ -97,61 +62,29 @@ def test_fastq_member_with_several_deflate_blocks(wave64):
     assert blocks[0] >= 2, blocks
 
 
-class Bits:
-    def __init__(self):
-        self.v, self.n = 0, 0
-
-    def put(self, value, nbits):                 # as the format packs numbers: least significant bit first
-        self.v |= value << self.n
-        self.n += nbits
-        return self
-
-    def code(self, value, nbits):                # a Huffman code: most significant bit first
-        for i in range(nbits - 1, -1, -1):
-            self.put((value >> i) & 1, 1)
-        return self
-
-    def bytes(self):
-        return self.v.to_bytes((self.n + 7) // 8, "little")
+@pytest.mark.parametrize("name", K.WELL_FORMED_NAMES)
+def test_every_well_formed_stream_is_zlibs_text(name):
+    """the table's own claim: every member, as a gzip member and as a raw stream, gives its text under zlib, whole"""
+    members, min_blocks = K.well_formed()[name]
+    for text, m in members:
+        assert zlib.decompress(m, 31) == text
+        d = zlib.decompressobj(-15)
+        assert d.decompress(m[18:-8]) == text and d.eof and d.unused_data == b""
+        assert struct.unpack("<II", m[-8:]) == (zlib.crc32(text), len(text)) and len(m) <= 65536 and len(text) <= 65536
 
 
-def fixed_lit(b, ch):
-    return b.code(0x30 + ch, 8) if ch < 144 else b.code(0x190 + ch - 144, 9)
-
-
-def crafted():
-    """name -> (payload, text the trailer names, the decoder's word)"""
-    c = {}
-    c["block type 3"] = (Bits().put(1, 1).put(3, 2).bytes(), b"", E.BAD_BLOCK_TYPE)
-    c["stored LEN / NLEN"] = (Bits().put(1, 1).put(0, 2).put(0, 5).put(3, 16).put(0xfffd, 16).bytes() + b"abc", b"abc", E.STORED_LEN)
-    c["stored past the payload"] = (Bits().put(1, 1).put(0, 2).put(0, 5).put(9, 16).put(0xfff6, 16).bytes() + b"abc", b"abcdefghi", E.IN_OVERRUN)
-    c["length symbol 286"] = (fixed_lit(Bits().put(1, 1).put(1, 2), 65).code(0xc6, 8).bytes(), b"A" * 4, E.BAD_LEN_SYM)
-    c["length symbol 287"] = (fixed_lit(Bits().put(1, 1).put(1, 2), 65).code(0xc7, 8).bytes(), b"A" * 4, E.BAD_LEN_SYM)
-    for d in (30, 31):
-        c["distance symbol %d" % d] = (fixed_lit(Bits().put(1, 1).put(1, 2), 65).code(1, 7).code(d, 5).bytes(), b"A" * 4, E.BAD_DIST_SYM)
-    c["distance before the member"] = (fixed_lit(Bits().put(1, 1).put(1, 2), 65).code(1, 7).code(1, 5).code(0, 7).bytes(), b"A" * 4, E.DIST_TOO_FAR)
-    good = fixed_lit(fixed_lit(Bits().put(1, 1).put(1, 2), 65), 66).code(0, 7).bytes()
-    c["text shorter than ISIZE"] = (good, b"ABC", E.OUT_SHORT)
-    c["text longer than ISIZE"] = (good, b"A", E.OUT_OVERRUN)
-    c["match longer than ISIZE"] = (fixed_lit(Bits().put(1, 1).put(1, 2), 65).code(2, 7).code(0, 5).code(0, 7).bytes(), b"AAAA", E.OUT_OVERRUN)
-    c["no end of block"] = (fixed_lit(Bits().put(1, 1).put(1, 2), 65).bytes()[:1], b"A", E.IN_OVERRUN)
-    # dynamic blocks: HLIT 257, HDIST 1, then the code-length code's lengths in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
-    dyn = lambda hclen: Bits().put(1, 1).put(2, 2).put(0, 5).put(0, 5).put(hclen - 4, 4)
-    c["code-length code over-subscribed"] = (dyn(4).put(1, 3).put(1, 3).put(1, 3).put(0, 3).bytes(), b"", E.OVER_SUBSCRIBED)
-    c["code-length code incomplete"] = (dyn(4).put(1, 3).put(0, 3).put(0, 3).put(0, 3).bytes(), b"", E.INCOMPLETE)
-    b = dyn(18)
-    for i in range(18):
-        b.put(1 if i in (15, 17) else 0, 3)          # lengths 1 for the symbols 2 and 1: "0" = a length of 1, "1" = a length of 2
-    over = Bits().put(b.v, b.n)
-    for _ in range(258):
-        over.put(0, 1)                               # 258 codes of one bit
-    c["length code over-subscribed"] = (over.bytes(), b"", E.OVER_SUBSCRIBED)
-    c["too many codes"] = (Bits().put(1, 1).put(2, 2).put(30, 5).put(0, 5).put(0, 4).bytes() + bytes(8), b"", E.TOO_MANY_CODES)
-    c["repeat without a length before it"] = (Bits().put(1, 1).put(2, 2).put(0, 5).put(0, 5).put(0, 4).put(1, 3).put(0, 3).put(0, 3).put(1, 3).put(1, 1).put(0, 2).bytes() + bytes(4), b"", E.BAD_REPEAT)
-    return c
-
-
-CRAFTED = crafted()
+@pytest.mark.parametrize("wave64", WAVES)
+@pytest.mark.parametrize("name", K.WELL_FORMED_NAMES)
+def test_well_formed_streams_of_the_formats_corners(name, wave64):
+    """the streams the device is given (tests/test_gpu_codec.py), between two short members and an empty one: the text, a status of 0
+    for every member, the deflate blocks the case claims"""
+    members, min_blocks = K.well_formed()[name]
+    good = E.bgzf_member(K.GOOD_NEIGHBOUR)
+    blocks = []
+    out, err, bad = inflate_members([good, E.bgzf_member(b"")] + [m for _, m in members] + [good], wave64, blocks)
+    assert bad is None and not err.any(), (bad, err)
+    assert out == K.GOOD_NEIGHBOUR + b"".join(t for t, _ in members) + K.GOOD_NEIGHBOUR
+    assert blocks[2] >= min_blocks, blocks
 
 
 @pytest.mark.parametrize("wave64", WAVES)
@@ -163,7 +96,7 @@ def test_corrupt_streams_end_in_a_status(name, wave64):
         assert d.decompress(payload) != text or not d.eof
     except zlib.error:
         pass
-    good = E.bgzf_member(b"the member before it\n")
+    good = E.bgzf_member(K.GOOD_NEIGHBOUR)
     blob = good + E.bgzf_member(text, payload=payload) + good
     table, n = E.member_table(blob)
     out, err, bad = E.inflate(blob, table, n, wave64)
@@ -173,33 +106,23 @@ def test_corrupt_streams_end_in_a_status(name, wave64):
 
 @pytest.mark.parametrize("wave64", WAVES)
 def test_crc_is_checked(wave64):
-    m = bytearray(E.bgzf_member(TEXT[:5000]))
-    m[-8] ^= 1
-    table, n = E.member_table(bytes(m))
-    out, err, bad = E.inflate(bytes(m), table, n, wave64)
-    assert bad == 0 and err[0] == E.CRC and out == TEXT[:5000]
+    m = K.crc_flip()
+    table, n = E.member_table(m)
+    out, err, bad = E.inflate(m, table, n, wave64)
+    assert bad == 0 and err[0] == E.CRC and out == K.CRC_TEXT == TEXT[:5000]
 
 
 @pytest.mark.parametrize("wave64", WAVES)
 @pytest.mark.parametrize("level", [0, 6])
 def test_single_byte_flips(level, wave64):
-    text = TEXT[:3000]
-    m = E.bgzf_member(text, level=level)
-    rng = random.Random(1234 + level)
+    text = K.FLIP_TEXT
     n_bad = 0
-    for _ in range(100):
-        at = rng.randrange(18, len(m) - 4)           # the payload and the CRC (the header and ISIZE are the host's to read)
-        x = bytearray(m)
-        x[at] ^= 1 << rng.randrange(8)
-        try:
-            d = zlib.decompressobj(-15)
-            ref = d.decompress(bytes(x[18:-8]))
-            ref_ok = d.eof and ref == text and struct.unpack_from("<I", x, len(x) - 8)[0] == zlib.crc32(text)
-        except zlib.error:
-            ref_ok = False
-        table, n = E.member_table(bytes(x))
-        out, err, bad = E.inflate(bytes(x), table, n, wave64)
-        assert (bad is None) == ref_ok, (at, err)
+    series = K.flips(level)
+    assert len(series) == 100 and len(text) == 3000
+    for x, ref_ok in series:
+        table, n = E.member_table(x)
+        out, err, bad = E.inflate(x, table, n, wave64)
+        assert (bad is None) == ref_ok, err
         if bad is None:
             assert out == text
         n_bad += bad is not None
