@@ -199,7 +199,7 @@ EXPORTS = [
     "cf_kreport_enable", "cf_kreport_reset", "cf_kreport_get", "cf_kreport_write", "cf_batch_kreport_ms", "cf_batch_text_names",
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
-    "cf_debug_prim_scan", "cf_debug_inflate", "cf_debug_deflate",
+    "cf_debug_prim_scan", "cf_debug_inflate", "cf_debug_deflate", "cf_batch_debug_text_reads",
 ]
 
 _lib = None
@@ -252,6 +252,7 @@ def lib():
         "cf_batch_num_rows": (i32, [vp, C.POINTER(u64)]), "cf_batch_results_compact": (i32, [vp, vp, u64, vp, vp]),
         "cf_batch_timings": (i32, [vp, C.POINTER(C.c_float * 5)]),
         "cf_batch_opcounts": (i32, [vp, C.POINTER(OpCounts)]), "cf_batch_debug_launch": (i32, [vp, C.POINTER(LaunchRecord)]),
+        "cf_batch_debug_text_reads": (i32, [vp, u64, vp, vp, vp, vp, u64, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
         "cf_counts_reset": (i32, [vp]), "cf_counts_get": (i32, [vp, vp, vp]), "cf_counts_device": (vp, [vp]), "cf_counts_allreduce": (i32, [vp, vp, vp]),
         "cf_debug_search": (i32, [vp, vp, u64, vp, vp, u32, vp]),
         "cf_debug_resolve": (i32, [vp, vp, u64, vp]),
@@ -898,6 +899,21 @@ class Slot:
     def launch_record(self):
         """which kernels the last batch was launched with (cf_batch_debug_launch) -> dict"""
         return _launch_record(self.L, self.h)
+
+    def text_reads(self, n_reads, n_words=None):
+        """what the device parser made of the slot's current text batch (cf_batch_debug_text_reads: copies, no kernel): per read
+        its length, seed, and the readID's place and length in the uploaded text; with n_words (the batch waited for) also the
+        packed 2-bit words and the N masks.  -> (len, seed, id_off, id_len) or (len, seed, id_off, id_len, words, nmask)"""
+        arr = [np.zeros(int(n_reads) + 1, dtype=np.uint32) for _ in range(4)]
+        nr, nw = C.c_uint64(0), C.c_uint64(0)
+        words = nmask = None
+        if n_words is not None:
+            words, nmask = np.zeros(int(n_words) + 1, dtype=np.uint64), np.zeros(int(n_words) + 1, dtype=np.uint32)
+        _check(self.L.cf_batch_debug_text_reads(self.h, int(n_reads), *[a.ctypes.data for a in arr], int(n_words or 0),
+                                                words.ctypes.data if words is not None else None, nmask.ctypes.data if nmask is not None else None,
+                                                C.byref(nr), C.byref(nw)))
+        out = tuple(a[:nr.value] for a in arr)
+        return out if words is None else out + (words[:nw.value], nmask[:nw.value])
 
     def close(self):
         if self.h:

@@ -3016,6 +3016,32 @@ cf_status cf_batch_debug_launch(const cf_batch *bt, cf_launch_record *out) {
     out->passes = bt->passes;
     return CF_OK;
 }
+// The reads the record pass (and, once the batch was waited for, k_text_pack) left in the slot, copied out as they lie there: no
+// kernel, no change of the slot's state.  (The upload waited for the record pass itself; the words are asked for behind a wait.)
+cf_status cf_batch_debug_text_reads(cf_batch *bt, uint64_t readCap, uint32_t *len, uint32_t *seed, uint32_t *idOff, uint32_t *idLen,
+                                    uint64_t wordCap, uint64_t *words, uint32_t *nmask, uint64_t *nReads, uint64_t *nWords) {
+    if (!bt || !nReads || !nWords || (words == nullptr) != (nmask == nullptr)) return CF_ERR_ARG;
+    *nReads = *nWords = 0;
+    if (!bt->loaded || !bt->fromText) { g_err = "cf_batch_debug_text_reads: the slot's reads did not come as text (cf_batch_upload_text): the record pass left nothing"; return CF_ERR_ARG; }
+    if (words && !bt->finished) { g_err = "cf_batch_debug_text_reads: the packed words are made by the plan stage: wait for the batch first"; return CF_ERR_ARG; }
+    if (bt->nReads > readCap || (words && bt->nWords > wordCap)) { g_err = "cf_batch_debug_text_reads: the output arrays are too small"; return CF_ERR_ARG; }
+    if (bt->nReads && (!len || !seed || !idOff || !idLen)) return CF_ERR_ARG;
+    return guard([&] {
+        HIP_OK(hipSetDevice(bt->cl->ix->device));
+        const uint64_t n = bt->nReads, w = bt->nWords;
+        if (n) {
+            HIP_OK(hipMemcpy(len, bt->rlen.p, 4 * n, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(seed, bt->seeds.p, 4 * n, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(idOff, bt->txIdOff.p, 4 * n, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(idLen, bt->txIdLen.p, 4 * n, hipMemcpyDeviceToHost));
+        }
+        if (words && w) {
+            HIP_OK(hipMemcpy(words, bt->bases.p, 8 * w, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(nmask, bt->nmask.p, 4 * w, hipMemcpyDeviceToHost));
+        }
+        *nReads = n; *nWords = w;
+    });
+}
 cf_status cf_batch_opcounts(cf_batch *bt, cf_opcounts *o) {
     if (!bt || !o) return CF_ERR_ARG;
     if (!bt->finished) { g_err = "the batch has not been classified"; return CF_ERR_ARG; }

@@ -742,6 +742,16 @@ typedef struct cf_launch_record {
     uint32_t split_sinks;      /* one bit per sink k_split_size / k_split_write were launched for (cf_batch_wait_text_split); 0: they were not */
 } cf_launch_record;
 cf_status cf_batch_debug_launch(const cf_batch *, cf_launch_record *);
+/* What the device parser made of the slot's current batch, read back for the tests: plain device-to-host copies of buffers the slot
+ * already holds — no kernel is launched and nothing of the slot changes.  Valid for a batch that came in as text
+ * (cf_batch_upload_text, _bgzf, _bgzf_pair) and was not refused; any other slot is CF_ERR_ARG.  Per read (*n_reads <= read_cap):
+ * its length, its seed (genRandSeed), and where its readID lies in the uploaded text (id_off, id_len: places in the slot's text
+ * buffer — the first block, head + inflated members, starts at 0, the mates' block at the next multiple of 64 behind the first
+ * block plus 128).  words / nmask (both or neither; *n_words <= word_cap): the packed 2-bit words and their N masks, read r's
+ * (len[r] + 31) / 32 words behind those of the reads before it; they are made by the plan stage, so asking for them before the batch
+ * was waited for is CF_ERR_ARG. */
+cf_status cf_batch_debug_text_reads(cf_batch *, uint64_t read_cap, uint32_t *len, uint32_t *seed, uint32_t *id_off, uint32_t *id_len,
+                                    uint64_t word_cap, uint64_t *words, uint32_t *nmask, uint64_t *n_reads, uint64_t *n_words);
 
 /* ------------------------------------------------------------ program entry
  * The whole classifier program as a call: the reference's own C symbol

@@ -962,18 +962,23 @@ uint32_t emu_text_parse2(const uint8_t *text, uint64_t nBytes, int format, uint3
                          uint32_t *rlen, uint32_t *seeds, uint32_t *seqOff, uint32_t *idOff, uint32_t *idLen, uint64_t *status,
                          uint32_t textBase, uint32_t stride, uint32_t mate) {
     const uint64_t nPieces = (nBytes + kTextPiece - 1) / kTextPiece;
-    std::vector<uint32_t> cnt(nPieces + 1, 0), pos(posCap + 1, 0);
+    // pos: posCap places and behind them a filled margin, which text_mark_body's guard must leave as it is (status[3] bit 63 otherwise)
+    constexpr uint64_t kMargin = 64;
+    constexpr uint32_t kFill = 0xA5A5A5A5u;
+    std::vector<uint32_t> cnt(nPieces + 1, 0), pos(posCap + kMargin, 0);
+    std::fill(pos.begin() + posCap, pos.end(), kFill);
     std::vector<uint64_t> base(nPieces + 1, 0);
     const DTextMark m{text, nBytes, format == (int)kTextFasta ? (uint32_t)'>' : (uint32_t)'\n', cnt.data(), base.data(), pos.data(), posCap};
     for (uint64_t t = 0; t < nPieces + 3; t++) text_count_body(m, t);
     for (uint64_t t = 0; t < nPieces; t++) base[t + 1] = base[t] + cnt[t];
     for (uint64_t t = 0; t < nPieces + 3; t++) text_mark_body(m, t);
+    for (uint64_t i = posCap; i < pos.size(); i++) if (pos[i] != kFill) status[3] |= 1ull << 63;
     TextStatus st{};
     const uint32_t seed0 = (globalSeed + 101u) * 59u * 61u * 67u * 71u * 73u * 79u * 83u;
     const DTextRec d{text, nBytes, pos.data(), &base[nPieces], posCap, recCap, (uint32_t)format, seed0, rlen, seeds, seqOff, idOff, idLen, &st, textBase, stride, mate};
     emuThreads((uint64_t)recCap + 70, [&](uint32_t r) { text_record_body(d, r); });
     status[0] += st.words(); status[1] += st.bases(); status[2] = std::max<uint64_t>(status[2], st.maxLen); status[3] |= st.flags;
-    if (st.flags) return 0;
+    if (status[3]) return 0;
     return (uint32_t)(format == (int)kTextFasta ? base[nPieces] : base[nPieces] >> 2);
 }
 void emu_text_pack(const uint8_t *text, uint32_t nReads, const uint32_t *seqOff, const uint32_t *rlen, uint64_t *bases, uint32_t *nmask) {

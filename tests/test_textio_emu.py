@@ -8,142 +8,69 @@ the one-lane build and as wavefronts of 64 lanes (their cross-lane sums) — aga
 * a plain Python statement of the default columns (aln_sink.h:2279-2337, readID aln_sink.h:2203-2217) and of the tally
   (aln_sink.h:142-172) for the formatter."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-import common
+import textcases as T
 from emu import emu
+from emu import emu_textio as E
+from textcases import FASTA, FASTQ, host_parse, make_records, read_id
 
-CLI = os.path.join(common.ROOT, "centrifuge_amd", "bin", "centrifuge-class")
-PAD = 128
-FASTA, FASTQ = 0, 1
+padded, vp = E.padded, E.vp
+PLAIN = T.plain_cases()
+IRREGULAR = T.irregular_cases()
+CAPACITY = T.capacity_cases()
 
 
 @pytest.fixture(params=[False, True], ids=["lane1", "wave64"])
 def L(request):
     was = emu.use_wave64(request.param)
-    lib = emu.lib()
-    lib.emu_text_parse.restype = C.c_uint32
-    lib.emu_text_parse.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32] + [C.c_void_p] * 6
-    lib.emu_text_pack.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib = E.lib(request.param)
     lib.emu_text_format.restype = C.c_uint64
+    # arrays as cf_batch_upload_text sizes them (recCap = total / 32 + 1024) in the one-lane build; the 64-lane build, which runs
+    # every thread of a launch as a fiber, gets arrays for the block's own records, as before
+    lib.upload_caps = not request.param
     yield lib
     emu.use_wave64(was)
 
 
-def padded(text):
-    a = np.zeros(len(text) + PAD + 64, dtype=np.uint8)
-    a[:len(text)] = np.frombuffer(text, dtype=np.uint8)
-    return a
-
-
-def vp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def parse(L, text, fmt, seed=0, rec_cap=None, pos_cap=None):
-    """-> (flags, reads) with reads = list of (readID bytes, bases str, seed) made from the bodies' outputs"""
-    buf = padded(text)
-    rec_cap = rec_cap if rec_cap is not None else (text.count(b">") if fmt == FASTA else text.count(b"\n") // 4) + 16
-    pos_cap = pos_cap if pos_cap is not None else (rec_cap if fmt == FASTA else 4 * rec_cap)
-    arr = [np.zeros(rec_cap + 80, dtype=np.uint32) for _ in range(5)]
-    status = np.zeros(4, dtype=np.uint64)
-    n = L.emu_text_parse(vp(buf), len(text), fmt, seed, pos_cap, rec_cap, *[vp(a) for a in arr], vp(status))
-    flags = int(status[3])
-    if flags:
-        return flags, None
-    rlen, seeds, seq_off, id_off, id_len = [a[:n] for a in arr]
-    assert int(status[0]) == int(((rlen.astype(np.uint64) + 31) // 32).sum()) and int(status[1]) == int(rlen.sum())
-    assert int(status[2]) == (int(rlen.max()) if n else 0)
-    n_words = int(status[0])
-    bases, nmask = np.zeros(n_words + 1, dtype=np.uint64), np.zeros(n_words + 1, dtype=np.uint32)
-    L.emu_text_pack(vp(buf), n, vp(seq_off), vp(rlen), vp(bases), vp(nmask))
-    out, w = [], 0
-    for r in range(n):
-        s = []
-        for i in range(int(rlen[r])):
-            word, j = w + i // 32, i % 32
-            s.append("N" if (int(nmask[word]) >> j) & 1 else "ACGT"[(int(bases[word]) >> (2 * j)) & 3])
-        w += (int(rlen[r]) + 31) // 32
-        out.append((bytes(text[int(id_off[r]):int(id_off[r]) + int(id_len[r])]), "".join(s), int(seeds[r])))
-    return 0, out
+    return E.parse(L, text, fmt, seed, rec_cap, pos_cap)
 
 
-def read_id(name):
-    """aln_sink.h:2203-2217"""
-    if len(name) >= 2 and name[-2:] in (b"/1", b"/2", b"/3"):
-        name = name[:-2]
-    for i, c in enumerate(name):
-        if c in b" \t\n\v\f\r":
-            return name[:i]
-    return name
-
-
-def host_parse(text, fmt, seed=0):
-    """the host parser through --dump-reads: None when it refuses the input, else (readID, bases, seed) per read"""
-    with tempfile.NamedTemporaryFile(suffix=".fa" if fmt == FASTA else ".fq") as f:
-        f.write(text)
-        f.flush()
-        r = subprocess.run([CLI, "--dump-reads", "-f" if fmt == FASTA else "-q", "--seed", str(seed), "-U", f.name], capture_output=True)
-    if r.returncode != 0:
-        return None
-    out = []
-    for ln in r.stdout.split(b"\n")[:-1]:
-        name, seq, _qual, sd = ln.rsplit(b"\t", 3)
-        out.append((read_id(name), seq.decode(), int(sd)))
-    return out
-
-
-def make_records(rng, n, fmt, wrap=0, lower=False, ns=True):
-    names, recs = [], []
-    for i in range(n):
-        ln = int(rng.integers(1, 300))
-        alphabet = "ACGTN" if ns and rng.random() < 0.3 else "ACGT"
-        seq = "".join(rng.choice(list(alphabet), ln))
-        if lower and rng.random() < 0.5:
-            seq = seq.lower()
-        name = ("r%d" % i).encode()
-        style = int(rng.integers(0, 7))
-        if style == 1:
-            name += b" some comment/here"
-        elif style == 2:
-            name += b"/1"
-        elif style == 3:
-            name += b"\tx/2"
-        elif style == 4:
-            name = b"sample/" + name + b"/3"
-        elif style == 5:
-            name += bytes([200, 255]) + b"x"             # bytes >= 128: the seed takes them sign-extended
-        names.append(name)
-        if fmt == FASTA:
-            body = seq if not wrap else "\n".join(seq[k:k + wrap] for k in range(0, ln, wrap))
-            recs.append(b">" + name + b"\n" + body.encode() + b"\n")
-        else:
-            qual = bytes(int(q) for q in rng.integers(33, 127, ln))
-            recs.append(b"@" + name + b"\n" + seq.encode() + b"\n+" + (name if rng.random() < 0.2 else b"") + b"\n" + qual + b"\n")
-    return b"".join(recs)
+def check_plain(L, c, seed, upload_caps):
+    """the block (or the two blocks of mates) is taken and gives the host parser's reads; upload_caps: arrays as cf_batch_upload_text sizes them"""
+    if c.text2 is not None:
+        flags, got = E.parse_mates(L, c.text, c.text2, c.fmt, seed)
+        w1, w2 = host_parse(c.text, c.fmt, seed), host_parse(c.text2, c.fmt, seed)
+        assert w1 is not None and w2 is not None and len(w1) == len(w2)
+        want = [w[q] for q in range(len(w1)) for w in (w1, w2)]
+    else:
+        caps = (T.rec_cap(len(c.text)), T.pos_cap(len(c.text), c.fmt)) if upload_caps else (None, None)
+        flags, got = parse(L, c.text, c.fmt, seed, *caps)
+        want = host_parse(c.text, c.fmt, seed)
+    assert flags == 0, (c.name, flags)
+    assert want is not None and got == want, c.name
 
 
 @pytest.mark.parametrize("fmt", [FASTA, FASTQ], ids=["fasta", "fastq"])
 def test_plain_blocks_parse_as_the_host_parser_does(L, fmt):
-    rng = np.random.default_rng(11 + fmt)
-    for trial, (n, wrap, lower) in enumerate([(1, 0, False), (3, 0, False), (70, 0, True), (200, 60, True), (130, 7, False), (64, 0, False), (65, 1, True)]):
-        text = make_records(rng, n, fmt, wrap=wrap if fmt == FASTA else 0, lower=lower)
-        for seed in (0, 12345):
-            flags, got = parse(L, text, fmt, seed)
-            assert flags == 0, (trial, flags)
-            want = host_parse(text, fmt, seed)
-            assert want is not None and got == want, trial
-    # a FASTA block whose last line has no '\n' is still plain (the sequence runs to the end of the block)
-    if fmt == FASTA:
-        text = b">a\nACGT\n>b x\nGGN"
-        assert parse(L, text, fmt) == (0, host_parse(text, fmt))
-    # an empty block: no reads, nothing flagged
+    for c in PLAIN:
+        if c.fmt == fmt and c.group == "trials":
+            for seed in T.SEEDS:
+                check_plain(L, c, seed, False)
     assert parse(L, b"", fmt) == (0, [])
+
+
+@pytest.mark.parametrize("group", sorted(set(c.group for c in PLAIN) - {"trials"}))
+def test_the_table_of_plain_blocks_parses_as_the_host_parser_does(L, group):
+    """the table's plain cases (tests/textcases.py), arrays sized as the upload sizes them: reads, bases, longest read, every readID,
+    every base, every seed"""
+    for c in PLAIN:
+        if c.group == group:
+            for seed in T.SEEDS:
+                check_plain(L, c, seed, L.upload_caps)
 
 
 @pytest.mark.parametrize("fmt", [FASTA, FASTQ], ids=["fasta", "fastq"])
@@ -153,88 +80,60 @@ def test_two_blocks_of_mates_in_one_buffer(L, fmt):
     rng = np.random.default_rng(31 + fmt)
     n = 97
     t1, t2 = make_records(rng, n, fmt, lower=True), make_records(rng, n, fmt, wrap=9 if fmt == FASTA else 0)
-    at2 = (len(t1) + 63) // 64 * 64 + PAD
-    buf = np.zeros(at2 + len(t2) + PAD + 64, dtype=np.uint8)
-    buf[:len(t1)] = np.frombuffer(t1, dtype=np.uint8)
-    buf[at2:at2 + len(t2)] = np.frombuffer(t2, dtype=np.uint8)
-    arr = [np.zeros(2 * n + 200, dtype=np.uint32) for _ in range(5)]
-    status = np.zeros(4, dtype=np.uint64)
-    L.emu_text_parse2.restype = C.c_uint32
-    L.emu_text_parse2.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint32] * 3
-    for m, (t, at) in enumerate(((t1, 0), (t2, at2))):
-        got = L.emu_text_parse2(buf.ctypes.data + at, len(t), fmt, 7, 4 * (n + 16), n + 16, *[vp(a) for a in arr], vp(status), at, 2, m)
-        assert got == n and not status[3]
-    rlen, seeds, seq_off, id_off, id_len = [a[:2 * n] for a in arr]
-    n_words = int(((rlen.astype(np.uint64) + 31) // 32).sum())
-    assert int(status[0]) == n_words and int(status[1]) == int(rlen.sum())
-    bases, nmask = np.zeros(n_words + 1, dtype=np.uint64), np.zeros(n_words + 1, dtype=np.uint32)
-    L.emu_text_pack(vp(buf), 2 * n, vp(seq_off), vp(rlen), vp(bases), vp(nmask))
+    flags, got = E.parse_mates(L, t1, t2, fmt, 7)
+    assert flags == 0 and len(got) == 2 * n
     want = [host_parse(t1, fmt, 7), host_parse(t2, fmt, 7)]
-    w = 0
-    whole = bytes(buf)
     for r in range(2 * n):
-        s = []
-        for i in range(int(rlen[r])):
-            word, j = w + i // 32, i % 32
-            s.append("N" if (int(nmask[word]) >> j) & 1 else "ACGT"[(int(bases[word]) >> (2 * j)) & 3])
-        w += (int(rlen[r]) + 31) // 32
-        assert (whole[int(id_off[r]):int(id_off[r]) + int(id_len[r])], "".join(s), int(seeds[r])) == want[r % 2][r // 2], r
+        assert got[r] == want[r % 2][r // 2], r
 
 
-IRREGULAR_FASTA = [
-    (b"\n>a\nACGT\n", 1), (b"#comment\n>a\nACGT\n", 1), (b"ACGT\n>a\nACGT\n", 1),      # does not start with '>'
-    (b">a\nACGT\n>b", 2), (b">a>b\nACGT\n", 2),                                           # a name line without its end
-    (b">\nACGT\n", 4),                                                                    # no name: the host names it by its ordinal
-    (b">a\r\nACGT\r\n", 8), (b">a\nAC\rGT\n", 16),
-    (b">a\nACRT\n", 16), (b">a\nAC-T\n", 16), (b">a\nAC.T\n", 16), (b">a\nAC GT\n", 16), (b">a\nAC*\n", 16),
-    (b">a\n>b\nACGT\n", 32), (b">a\n\n>b\nACGT\n", 32), (b">a\nACGT\n>b\n", 32),
-]
-IRREGULAR_FASTQ = [
-    (b"\n@a\nACGT\n+\nIIII\n", 1), (b"x\n@a\nACGT\n+\nIIII\n", 1),
-    (b"@a\nACGT\n+\nIIII", 512), (b"@a\nACGT\n+\nIIII\n\n", 512), (b"@a\nAC\nGT\n+\nIIII\n", 512),
-    (b"@\nACGT\n+\nIIII\n", 4), (b"@a\r\nACGT\r\n+\r\nIIII\r\n", 8),
-    (b"@a\nAC.T\n+\nIIII\n", 16), (b"@a\nACRT\n+\nIIII\n", 16), (b"@a\nAC T\n+\nIIII\n", 16),
-    (b"@a\n\n+\n\n", 32),
-    (b"@a\nACGT\n-\nIIII\n", 64), (b"@a\nACGT\n\nIIII\n", 64),
-    (b"@a\nACGT\n+\nIII\n", 128), (b"@a\nACGT\n+\nIIIII\n", 128),
-    (b"@a\nACGT\n+\nII I\n", 256), (b"@a\nACGT\n+\nII\tI\n", 256),
-    (b"@a\nAC\nGT\n+\nII\nII\n@b\nAC\n", 1 | 64),                                      # wrapped lines: the line count happens to fit
-]
-
-
-@pytest.mark.parametrize("fmt,cases", [(FASTA, IRREGULAR_FASTA), (FASTQ, IRREGULAR_FASTQ)], ids=["fasta", "fastq"])
-def test_everything_the_host_parser_treats_specially_is_flagged(L, fmt, cases):
-    good = make_records(np.random.default_rng(5), 70, fmt)
-    for text, bit in cases:
-        for block in (text, good + text):
-            if block is not text and (bit & 1 or text[:1] in (b"\n", b"#", b"x", b"A")):
-                continue                                      # (what is only wrong at the start of a block)
-            flags, _ = parse(L, block, fmt)
-            assert flags & bit == bit or (flags and bit == 512), (text, flags, bit)
+@pytest.mark.parametrize("fmt", [FASTA, FASTQ], ids=["fasta", "fastq"])
+def test_everything_the_host_parser_treats_specially_is_flagged(L, fmt):
+    """every irregular block of the table — alone, behind 70 records, and as record 0, 63, 64, 255, 256 and 300 of 300 — carries its bit"""
+    seen = 0
+    for c in IRREGULAR:
+        if c.fmt == fmt:
+            caps = (T.rec_cap(len(c.text)), T.pos_cap(len(c.text), fmt)) if L.upload_caps else (None, None)
+            flags, _ = parse(L, c.text, fmt, 0, *caps)
+            assert T.carries(flags, c.bit), (c.name, flags, c.bit)
+            seen |= flags
+    # every reason bit of the format is reached
+    assert seen & 0x7ff == (0x3f if fmt == FASTA else 0x3ff), hex(seen)
     # too many records / markers for the arrays: left to the host as well
     text = make_records(np.random.default_rng(6), 50, fmt)
     assert parse(L, text, fmt, rec_cap=49)[0] & 1024
     assert parse(L, text, fmt, rec_cap=50)[0] == 0
 
 
+def test_the_capacity_table_is_the_formula():
+    """CAPACITY's counts against recCap = total / 32 + 1024 (tests/textcases.py's docstring); the library is not called"""
+    for fmt in (FASTA, FASTQ):
+        for unit, n, fits in T.CAPACITY[fmt]:
+            total = len(unit) * n
+            records = unit.count(b">") * n if fmt == FASTA else unit.count(b"\n") * n // 4
+            markers = (unit.count(b">") if fmt == FASTA else unit.count(b"\n")) * n
+            cap = total // 32 + 1024
+            assert (records <= cap and markers <= (cap if fmt == FASTA else 4 * cap)) == fits, (unit, n)
+        # the edge itself: each unit's largest fitting count is followed by its smallest refused one
+        for unit in set(u for u, _, _ in T.CAPACITY[fmt]):
+            ok = max(n for u, n, f in T.CAPACITY[fmt] if u == unit and f)
+            assert (unit, ok + 1, False) in T.CAPACITY[fmt]
+        assert T.FLOOD > 4 * (T.FLOOD // 32 + 1024)
+
+
+@pytest.mark.parametrize("c", CAPACITY, ids=[c.name for c in CAPACITY])
+def test_a_block_beyond_the_upload_capacity_is_too_many_and_nothing_else(L, c):
+    """arrays sized by the upload's formula, a filled margin behind each (E.parse checks the margins): text_mark_body's guard and
+    text_counts leave a block with more markers than posCap alone"""
+    total = len(c.text)
+    assert parse(L, c.text, c.fmt, 0, T.rec_cap(total), T.pos_cap(total, c.fmt))[0] == T.TOO_MANY
+
+
 @pytest.mark.parametrize("fmt", [FASTA, FASTQ], ids=["fasta", "fastq"])
 def test_mutated_blocks_are_either_flagged_or_parsed_as_the_host_parser_does(L, fmt):
     """the safety property of the plain form: whatever a block looks like, if the device takes it, its reads are the host parser's"""
-    rng = np.random.default_rng(2024 + fmt)
-    junk = [b"\r", b">", b"@", b"+", b"\n", b".", b"-", b"R", b"n", b" ", b"\t", b"/", b"/1", b"\n\n", b"*", b"a", b"\x00", b"\xff"]
     taken = 0
-    for trial in range(160):
-        text = bytearray(make_records(rng, int(rng.integers(1, 8)), fmt, wrap=int(rng.choice([0, 0, 5])) if fmt == FASTA else 0, lower=True))
-        for _ in range(int(rng.integers(1, 4))):
-            at = int(rng.integers(0, len(text) + 1))
-            kind = int(rng.integers(0, 3))
-            if kind == 0:
-                text[at:at] = junk[int(rng.integers(0, len(junk)))]
-            elif kind == 1 and at < len(text):
-                del text[at:at + int(rng.integers(1, 4))]
-            elif at < len(text):
-                text[at:at + 1] = junk[int(rng.integers(0, len(junk)))]
-        text = bytes(text)
+    for trial, text in enumerate(T.mutated(fmt)):
         flags, got = parse(L, text, fmt)
         if flags:
             continue
