@@ -199,7 +199,7 @@ EXPORTS = [
     "cf_kreport_enable", "cf_kreport_reset", "cf_kreport_get", "cf_kreport_write", "cf_batch_kreport_ms", "cf_batch_text_names",
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
-    "cf_debug_prim_scan", "cf_debug_inflate", "cf_debug_deflate", "cf_batch_debug_text_reads",
+    "cf_debug_prim_scan", "cf_debug_inflate", "cf_debug_deflate", "cf_batch_debug_text_reads", "cf_debug_format", "cf_debug_split",
 ]
 
 _lib = None
@@ -308,6 +308,7 @@ def lib():
         "cf_debug_prim_scan": (i32, [i32, i32, i32, vp, u64, vp]),
         "cf_debug_inflate": (i32, [i32, i32, cp, u64, u64, u64, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int64)]),
         "cf_debug_deflate": (i32, [i32, cp, u64, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]),
+        "cf_debug_format": (i32, [i32, vp, vp]), "cf_debug_split": (i32, [i32, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1057,6 +1058,100 @@ def debug_deflate(text, member=65280, device=0):
     n, nm = C.c_uint64(0), C.c_uint64(0)
     _check(lib().cf_debug_deflate(device, text, len(text), member, out.ctypes.data, out.size - 1, C.byref(n), sizes.ctypes.data, n_members, C.byref(nm)))
     return out[:n.value].tobytes(), sizes[:nm.value].copy()
+
+
+class DebugBlock(C.Structure):
+    """cf_debug_block"""
+    _fields_ = [("text", C.c_void_p), ("text_bytes", C.c_uint64), ("id_off", C.c_void_p), ("id_len", C.c_void_p), ("rlen", C.c_void_p),
+                ("qual_off", C.c_void_p), ("bases", C.c_void_p), ("nmask", C.c_void_p), ("qinfo", C.c_void_p),
+                ("n_queries", C.c_uint32), ("paired", C.c_uint32)]
+
+
+class DebugFormatIn(C.Structure):
+    """cf_debug_format_in"""
+    _fields_ = [("block", DebugBlock), ("rows", C.c_void_p), ("score2", C.c_void_p), ("max_score", C.c_void_p),
+                ("strs", C.c_void_p), ("strs_bytes", C.c_uint64), ("uid_off", C.c_void_p), ("rank_off", C.c_void_p), ("tax_off", C.c_void_p),
+                ("tax_leaf", C.c_void_p), ("n_refs", C.c_uint32), ("n_taxa", C.c_uint32), ("idx_zero", C.c_uint32), ("n_cols", C.c_uint32),
+                ("tax_strs", C.c_void_p), ("tax_strs_bytes", C.c_uint64), ("trank_off", C.c_void_p), ("tname_off", C.c_void_p),
+                ("cols", C.c_void_p), ("out_cap", C.c_uint64), ("tuples_cap", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class DebugFormatOut(C.Structure):
+    """cf_debug_format_out"""
+    _fields_ = [("text", C.c_void_p), ("size", C.c_void_p), ("single", C.c_void_p), ("tuples", C.c_void_p),
+                ("total", C.c_uint64), ("tuple_words", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class DebugSplitOut(C.Structure):
+    """cf_debug_split_out"""
+    _fields_ = [("text", C.c_void_p * 4), ("cap", C.c_uint64 * 4), ("bytes", C.c_uint64 * 4), ("records", C.c_uint64 * 4), ("sized", C.c_uint32 * 4)]
+
+
+DEBUG_UNWRITTEN = 0x5A       # what a byte of a tap's output room holds that no kernel wrote
+
+
+def _debug_block(batch, keep):
+    """batch: a block's text and what a batch leaves per read and per query (the dict the CPU harness of the egress stage takes)"""
+    def arr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        if a.size == 0:
+            a = np.zeros(1, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+    b = DebugBlock()
+    b.text, b.text_bytes = arr(np.frombuffer(bytes(batch["text"]), dtype=np.uint8), np.uint8), len(batch["text"])
+    b.id_off, b.id_len, b.rlen = arr(batch["idOff"], np.uint32), arr(batch["idLen"], np.uint32), arr(batch["rlen"], np.uint32)
+    b.qual_off = arr(batch.get("qualOff"), np.uint32)
+    b.bases, b.nmask, b.qinfo = arr(batch["bases"], np.uint64), arr(batch["nmask"], np.uint32), arr(batch["qinfo"], np.uint8)
+    b.n_queries, b.paired = len(batch["qinfo"]), int(batch["paired"])
+    return b, arr
+
+
+def debug_format(world, batch, cols, out_cap, tuples_cap=None, device=0):
+    """The device formatter on its own (cf_debug_format), through the launch code of cf_batch_wait_text.  world: the string tables,
+    batch: the block, the rows and what a batch leaves per read and per query (the dicts the CPU harness takes); cols: column codes,
+    none: the default eight's own kernels.  -> the room's out_cap bytes (DEBUG_UNWRITTEN where nothing was written), the bytes per
+    query, the bytes the size pass summed, the perfect single assignments per dense taxon (n_taxa + 1 words), the tuple words that
+    fit tuples_cap, the words all tuples need.  CfError: a limit, or a margin around a device buffer changed."""
+    keep = []
+    x = DebugFormatIn()
+    x.block, arr = _debug_block(batch, keep)
+    nq = len(batch["qinfo"])
+    x.rows, x.score2, x.max_score = arr(batch["rows"], np.uint32), arr(batch["score2"], np.uint32), arr(batch["maxScore"], np.uint32)
+    x.strs, x.strs_bytes = arr(np.frombuffer(bytes(world["strs"]), dtype=np.uint8), np.uint8), len(world["strs"])
+    x.uid_off, x.rank_off, x.tax_off = arr(world["uidOff"], np.uint32), arr(world["rankOff"], np.uint32), arr(world["taxOff"], np.uint32)
+    x.tax_leaf = arr(world["taxLeaf"], np.uint8)
+    x.n_refs, x.n_taxa, x.idx_zero = world["nRefs"], world["nTaxa"], world["idxZero"]
+    x.tax_strs, x.tax_strs_bytes = arr(np.frombuffer(bytes(world["taxStrs"]), dtype=np.uint8), np.uint8), len(world["taxStrs"])
+    x.trank_off, x.tname_off = arr(world["trankOff"], np.uint32), arr(world["tnameOff"], np.uint32)
+    x.cols, x.n_cols = arr(np.asarray(cols, dtype=np.uint8), np.uint8), len(cols)
+    x.out_cap = int(out_cap)
+    x.tuples_cap = nq * 64 + 16 if tuples_cap is None else int(tuples_cap)
+    text, size = np.zeros(x.out_cap + 1, dtype=np.uint8), np.zeros(nq + 1, dtype=np.uint32)
+    single, tuples = np.zeros(world["nTaxa"] + 1, dtype=np.uint64), np.zeros(x.tuples_cap + 1, dtype=np.uint32)
+    y = DebugFormatOut()
+    y.text, y.size, y.single, y.tuples = text.ctypes.data, size.ctypes.data, single.ctypes.data, tuples.ctypes.data
+    _check(lib().cf_debug_format(device, C.byref(x), C.byref(y)))
+    if nq == 0:
+        text[:] = DEBUG_UNWRITTEN
+    return text[:x.out_cap].tobytes(), size[:nq].copy(), int(y.total), single, tuples[:min(y.tuple_words, x.tuples_cap)].copy(), int(y.tuple_words)
+
+
+def debug_split(batch, sinks, cap=1 << 22, device=0):
+    """The device read splitter on its own (cf_debug_split), through the launch code of cf_batch_wait_text_split.  batch: as
+    debug_format takes it; sinks: the SPLIT_* bits; cap: the room of every sink, or four of them.  -> per sink (the first
+    min(bytes sized, room) bytes of its room — DEBUG_UNWRITTEN where nothing was written —, the bytes sized, the records, sized)"""
+    keep = []
+    blk, _ = _debug_block(batch, keep)
+    caps = [int(cap)] * 4 if np.isscalar(cap) else [int(c) for c in cap]
+    y = DebugSplitOut()
+    outs = [np.zeros(c + 1, dtype=np.uint8) for c in caps]
+    for s in range(4):
+        y.text[s], y.cap[s] = outs[s].ctypes.data, caps[s]
+    _check(lib().cf_debug_split(device, C.byref(blk), int(sinks), C.byref(y)))
+    return [(outs[s][:min(y.bytes[s], caps[s])].tobytes(), int(y.bytes[s]), int(y.records[s]), bool(y.sized[s])) for s in range(4)]
 
 
 class Report:

@@ -1564,6 +1564,7 @@ uint32_t cf_gen_rand_seed(const uint8_t *seq, const uint8_t *qual, uint64_t len,
 // ------------------------------------------------------------------ a batch, stage by stage
 // Everything below enqueues on one stream and returns; only waitBatch() blocks.
 
+constexpr uint64_t kBatchWordPad = 16;       // words (and N masks) a slot keeps behind the batch's packed reads
 // Sizes every buffer of the slot for a batch of nReads reads in nWords packed words (maxLen = longest read,
 // nBases = sum of the lengths or 0 when unknown).  Buffers only grow; nothing here touches a stream.
 static void sizeBatch(cf_batch *bt, uint64_t nReads, uint64_t nWords, uint64_t nBases, uint32_t maxLen, int paired) {
@@ -1575,7 +1576,7 @@ static void sizeBatch(cf_batch *bt, uint64_t nReads, uint64_t nWords, uint64_t n
     bt->nReads = nReads; bt->paired = paired ? 1 : 0; bt->nQueries = paired ? nReads / 2 : nReads; bt->nWords = nWords;
     bt->maxLenHost = maxLen;
     const uint64_t nq = bt->nQueries;
-    bt->bases.ensure(nWords + 16); bt->nmask.ensure(nWords + 16);      // (the search kernel reads a read's words in whole 16-byte pieces, W words from its first)
+    bt->bases.ensure(nWords + kBatchWordPad); bt->nmask.ensure(nWords + kBatchWordPad);      // (the search kernel reads a read's words in whole 16-byte pieces, W words from its first)
     bt->rlen.ensure(nReads + 16); bt->seeds.ensure(nReads + 1); bt->woff.ensure(nReads + 1);
     bt->pass.ensure(nReads + 1); bt->hitCap.ensure(nReads + 16);
     bt->slotOf.ensure(nReads + 1); bt->hitBase.ensure(nReads + 1); bt->items.ensure(nReads + 1);
@@ -2611,6 +2612,29 @@ static void enqueueDeflate(uint8_t *text, uint64_t nBytes, uint32_t member, uint
     HIP_OK(hipMemcpyAsync(hTotal, zOff + nMembers, 8, hipMemcpyDeviceToHost, st));
 }
 
+// The text of a batch's rows (cf_textio.hpp "egress"), on st: the size pass — pc.nCols == 0: the default eight's bodies —, the
+// exclusive sums of the sizes into outOff[0 .. nQueries], their total fetched through *hTotal and WAITED for; room(total) then
+// names f.out and f.outCap, and the write pass is queued behind it.  Blocks of 256 threads: fmt_wave_lds keeps a stage per
+// wavefront of such a block.  f.nQueries > 0; returns the total.  (cf_batch_wait_text and cf_debug_format)
+extern "C++" {
+template <typename Room>
+static uint64_t enqueueFormat(DTextFmt &f, const TextCols &pc, uint64_t *outOff, uint64_t *tileA, uint32_t *tileC, uint64_t *hTotal, hipStream_t st, Room room) {
+    const uint64_t nq = f.nQueries;
+    const dim3 bl(256), gq((unsigned)((nq + 255) / 256));
+    f.outOff = outOff;
+    if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_size, gq, bl, 0, st, f, pc);
+    else hipLaunchKernelGGL(k_fmt_size, gq, bl, 0, st, f);
+    scan_enqueue<SCAN_PLAIN>(f.size, nq, outOff, nullptr, tileA, tileC, st);
+    HIP_OK(hipMemcpyAsync(hTotal, outOff + nq, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const uint64_t total = *hTotal;
+    room(total);
+    if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_write, gq, bl, 0, st, f, pc);
+    else hipLaunchKernelGGL(k_fmt_write, gq, bl, 0, st, f);
+    return total;
+}
+}  // extern "C++"
+
 // The results of a batch that came as text, as text: the default columns formatted on the device from the rows the kernels left
 // there (none of them crosses the link), and the perfect multi-assignment tuples the report's EM needs beside the device's counters.
 static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_t *textBytes) {
@@ -2680,19 +2704,14 @@ static cf_status waitText(cf_batch *bt, cf_results_text *res, bool bgzf, uint64_
         }
         bt->deflateMs = 0;
         if (nq) {
-            if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_size, gq, bl, 0, st, f, pc);
-            else hipLaunchKernelGGL(k_fmt_size, gq, bl, 0, st, f);
-            scan_enqueue<SCAN_PLAIN>(bt->txSize.p, nq, bt->txOutOff.p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
-            HIP_OK(hipMemcpyAsync(bt->hTxTotal.p, bt->txOutOff.p + nq, 8, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            total = plain = *bt->hTxTotal.p;
-            // (BGZF: the members are moved together into the room the text lay in — it has been read by then)
-            const uint64_t nMembers = bgzf ? (total + member - 1) / member : 0, room = std::max<uint64_t>(total + kInfPad, nMembers * def_stride(member));
-            bt->textOut.ensure(room);
-            bt->hTextOut.ensure((bgzf ? nMembers * def_stride(member) : total) + 16);      // (BGZF: the members' bound — no pinned memory is made between the two waits below)
-            f.out = bt->textOut.p; f.outCap = total;
-            if (pc.nCols) hipLaunchKernelGGL(k_fmt_cols_write, gq, bl, 0, st, f, pc);
-            else hipLaunchKernelGGL(k_fmt_write, gq, bl, 0, st, f);
+            uint64_t nMembers = 0;
+            total = plain = enqueueFormat(f, pc, bt->txOutOff.p, bt->txTileA.p, bt->txTileC.p, bt->hTxTotal.p, st, [&](uint64_t sum) {
+                // (BGZF: the members are moved together into the room the text lay in — it has been read by then)
+                nMembers = bgzf ? (sum + member - 1) / member : 0;
+                bt->textOut.ensure(std::max<uint64_t>(sum + kInfPad, nMembers * def_stride(member)));
+                bt->hTextOut.ensure((bgzf ? nMembers * def_stride(member) : sum) + 16);      // (BGZF: the members' bound — no pinned memory is made between the two waits below)
+                f.out = bt->textOut.p; f.outCap = sum;
+            });
             if (bgzf && nMembers) {
                 bt->zOut.ensure(nMembers * def_stride(member)); bt->zOutSize.ensure(nMembers + 16); bt->zOutOff.ensure(nMembers + 16);
                 bt->txTileA.ensure(scan_tiles_for(nMembers) + 1); bt->txTileC.ensure(scan_tiles_for(nMembers) + 1);
@@ -2737,6 +2756,40 @@ cf_status cf_batch_set_text_split(cf_batch *bt, uint32_t sinks, int32_t bgzf) {
     bt->splitSinks = sinks; bt->splitBgzf = sinks && bgzf;
     return CF_OK;
 }
+// one bit per sink that is sized and written (split_sink_on)
+static uint32_t splitSinkMask(uint32_t sinks, bool paired) {
+    uint32_t mask = 0;
+    for (uint32_t s = 0; s < kSplitSinks; s++) if (((sinks >> (s >> 1)) & 1u) && (paired || !(s & 1u))) mask |= 1u << s;
+    return mask;
+}
+// The split of a batch's reads, on st: the records' tally zeroed, the size pass, per sink of `mask` the exclusive sums of d.size[s]
+// into off[s][0 .. nQueries]; the sums' totals (tot[s]) and the records (tot[kSplitSinks + s]) fetched and WAITED for; room(tot)
+// then names d.out[s] and d.cap[s], and the write pass is queued behind it.  Blocks of 256 threads.  ev: four events, around the
+// size pass with its sums and around the write pass, or nullptr.  d.nQueries > 0.  (cf_batch_wait_text_split and cf_debug_split)
+extern "C++" {
+template <typename Room>
+static void enqueueSplit(DTextSplit &d, uint32_t mask, uint64_t *const *off, uint64_t *tileA, uint32_t *tileC, uint64_t *tot, hipEvent_t *ev, hipStream_t st, Room room) {
+    const uint64_t nq = d.nQueries;
+    const dim3 bl(256), gq((unsigned)((nq + 255) / 256));
+    HIP_OK(hipMemsetAsync(d.nRec, 0, kSplitSinks * sizeof(unsigned long long), st));
+    if (ev) HIP_OK(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_split_size, gq, bl, 0, st, d);
+    for (uint32_t s = 0; s < kSplitSinks; s++) {
+        if (!(mask >> s & 1u)) continue;
+        d.off[s] = off[s];
+        scan_enqueue<SCAN_PLAIN>(d.size[s], nq, off[s], nullptr, tileA, tileC, st);
+        HIP_OK(hipMemcpyAsync(tot + s, off[s] + nq, 8, hipMemcpyDeviceToHost, st));
+    }
+    if (ev) HIP_OK(hipEventRecord(ev[1], st));
+    HIP_OK(hipMemcpyAsync(tot + kSplitSinks, d.nRec, kSplitSinks * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    room(tot);
+    if (ev) HIP_OK(hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(k_split_write, gq, bl, 0, st, d);
+    if (ev) HIP_OK(hipEventRecord(ev[3], st));
+}
+}  // extern "C++"
+
 cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
     if (!bt || !out) return CF_ERR_ARG;
     if (bt->resultFormat != CF_RESULTS_NARROW) { g_err = "cf_batch_wait_text_split needs a slot whose result format is CF_RESULTS_NARROW"; return CF_ERR_ARG; }
@@ -2756,13 +2809,13 @@ cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
             d.text = bt->text.p; d.idOff = bt->txIdOff.p; d.idLen = bt->txIdLen.p; d.rlen = bt->rlen.p; d.qinfo = bt->qinfo.p;
             d.woff = bt->woff.p; d.bases = bt->bases.p; d.nmask = bt->nmask.p; d.qualOff = bt->textFastq ? bt->txQualOff.p : nullptr;
             d.nQueries = (uint32_t)nq; d.paired = (uint32_t)bt->paired; d.sinks = bt->splitSinks;
-            uint32_t mask = 0;
+            const uint32_t mask = splitSinkMask(d.sinks, d.paired != 0);
+            uint64_t *off[kSplitSinks] = {};
             for (uint32_t s = 0; s < kSplitSinks; s++) {
                 bt->spBytes[s] = bt->spPlain[s] = bt->spRecords[s] = 0;
-                if (!((d.sinks >> (s >> 1)) & 1u) || (!d.paired && (s & 1u))) continue;      // (split_sink_on)
-                mask |= 1u << s;
+                if (!(mask >> s & 1u)) continue;
                 bt->spSize[s].ensure(nq + 16); bt->spOff[s].ensure(nq + 16);
-                d.size[s] = bt->spSize[s].p; d.off[s] = bt->spOff[s].p;
+                d.size[s] = bt->spSize[s].p; off[s] = bt->spOff[s].p;
             }
             bt->splitMs = 0;
             if (nq) {
@@ -2770,39 +2823,26 @@ cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
                 bt->txTileA.ensure(scan_tiles_for(nq) + 1); bt->txTileC.ensure(scan_tiles_for(nq) + 1);
                 d.nRec = bt->spRec.p;
                 for (auto &e : bt->evSplit) if (!e) HIP_OK(hipEventCreate(&e));
-                const dim3 bl(256), gq((unsigned)((nq + 255) / 256));
                 uint64_t *const tot = bt->hSpTotal.p;
                 std::memset(tot, 0, 3 * kSplitSinks * 8);
-                HIP_OK(hipMemsetAsync(bt->spRec.p, 0, kSplitSinks * sizeof(unsigned long long), st));
-                HIP_OK(hipEventRecord(bt->evSplit[0], st));
-                hipLaunchKernelGGL(k_split_size, gq, bl, 0, st, d);
-                for (uint32_t s = 0; s < kSplitSinks; s++) {
-                    if (!(mask >> s & 1u)) continue;
-                    scan_enqueue<SCAN_PLAIN>(bt->spSize[s].p, nq, bt->spOff[s].p, nullptr, bt->txTileA.p, bt->txTileC.p, st);
-                    HIP_OK(hipMemcpyAsync(tot + s, bt->spOff[s].p + nq, 8, hipMemcpyDeviceToHost, st));
-                }
-                HIP_OK(hipEventRecord(bt->evSplit[1], st));
-                HIP_OK(hipMemcpyAsync(tot + kSplitSinks, bt->spRec.p, kSplitSinks * 8, hipMemcpyDeviceToHost, st));
-                HIP_OK(hipStreamSynchronize(st));
-                // the sinks' sizes are known: their room (outside the timed stretches: a buffer that grows is allocated here)
                 uint64_t nMembers[kSplitSinks] = {};
-                for (uint32_t s = 0; s < kSplitSinks; s++) {
-                    if (!(mask >> s & 1u)) continue;
-                    const uint64_t total = tot[s], nm = bgzf ? (total + member - 1) / member : 0;
-                    nMembers[s] = nm;
-                    // (BGZF: the members are moved together into the room the text lay in, as cf_batch_wait_text_bgzf's are)
-                    bt->spOut[s].ensure(std::max<uint64_t>(total + kInfPad, nm * def_stride(member)) + 8);
-                    bt->hSpOut[s].ensure((bgzf ? nm * def_stride(member) : total) + 16);
-                    if (nm) {
-                        bt->spZ[s].ensure(nm * def_stride(member)); bt->spZSize[s].ensure(nm + 16); bt->spZOff[s].ensure(nm + 16);
-                        bt->spTileA[s].ensure(scan_tiles_for(nm) + 1); bt->spTileC[s].ensure(scan_tiles_for(nm) + 1);
+                enqueueSplit(d, mask, off, bt->txTileA.p, bt->txTileC.p, tot, bt->evSplit, st, [&](const uint64_t *) {
+                    // the sinks' sizes are known: their room (outside the timed stretches: a buffer that grows is allocated here)
+                    for (uint32_t s = 0; s < kSplitSinks; s++) {
+                        if (!(mask >> s & 1u)) continue;
+                        const uint64_t total = tot[s], nm = bgzf ? (total + member - 1) / member : 0;
+                        nMembers[s] = nm;
+                        // (BGZF: the members are moved together into the room the text lay in, as cf_batch_wait_text_bgzf's are)
+                        bt->spOut[s].ensure(std::max<uint64_t>(total + kInfPad, nm * def_stride(member)) + 8);
+                        bt->hSpOut[s].ensure((bgzf ? nm * def_stride(member) : total) + 16);
+                        if (nm) {
+                            bt->spZ[s].ensure(nm * def_stride(member)); bt->spZSize[s].ensure(nm + 16); bt->spZOff[s].ensure(nm + 16);
+                            bt->spTileA[s].ensure(scan_tiles_for(nm) + 1); bt->spTileC[s].ensure(scan_tiles_for(nm) + 1);
+                        }
+                        d.out[s] = bt->spOut[s].p; d.cap[s] = total;
+                        bt->spPlain[s] = total; bt->spRecords[s] = tot[kSplitSinks + s];
                     }
-                    d.out[s] = bt->spOut[s].p; d.cap[s] = total;
-                    bt->spPlain[s] = total; bt->spRecords[s] = tot[kSplitSinks + s];
-                }
-                HIP_OK(hipEventRecord(bt->evSplit[2], st));
-                hipLaunchKernelGGL(k_split_write, gq, bl, 0, st, d);
-                HIP_OK(hipEventRecord(bt->evSplit[3], st));
+                });
                 // plain: the text comes back as it is.  BGZF: every sink's deflate, sums and compaction are queued with buffers of
                 // their own, so that the host waits once for all the sinks' sizes and then fetches the members
                 for (uint32_t s = 0; s < kSplitSinks; s++) {
@@ -3470,6 +3510,175 @@ cf_status cf_debug_deflate(int device, const void *text, uint64_t n_bytes, uint3
             if (sizes[m] > def_stride(member)) throw std::logic_error("a BGZF member outgrew its room");
             for (uint64_t i = sizes[m]; i < def_stride(member); i++)
                 if (rooms[m * def_stride(member) + i] != kTapUnwritten) throw std::runtime_error("a byte behind member " + std::to_string(m) + " in its room was changed");
+        }
+    });
+}
+
+// The egress stage on its own.  What a batch leaves on the device for it, from the host: the text with the upload's kTextPad zero
+// bytes behind it, the packed reads with the slot's kBatchWordPad words behind them (filled: nothing may depend on what they
+// hold), the per-read and per-query arrays with the slot's spare entries; woff summed here as the plan stage sums it.
+extern "C++" {
+struct TapBlock {
+    DevBuf<uint8_t> text, qinfo;
+    DevBuf<uint32_t> idOff, idLen, rlen, qualOff, nmask;
+    DevBuf<uint64_t> bases, woff;
+    uint64_t nq = 0, nReads = 0, nWords = 0;
+    template <typename T>
+    static void put(DevBuf<T> &b, const T *src, uint64_t n, uint64_t spare, int fill) {
+        b.alloc(n + spare);
+        HIP_OK(hipMemset(b.p, fill, (n + spare) * sizeof(T)));
+        if (n) HIP_OK(hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    }
+    void make(const cf_debug_block &b, const char *who) {
+        nq = b.n_queries; nReads = b.paired ? 2 * nq : nq;
+        if (!b.text || !b.id_off || !b.id_len || !b.rlen || !b.bases || !b.nmask || !b.qinfo) throw ArgError(std::string(who) + ": a null array of the block");
+        if (b.text_bytes >= 0xffff0000ull) throw ArgError(std::string(who) + ": the text holds fewer than 2^32 - 65536 bytes");
+        std::vector<uint64_t> hw(nReads + 1, 0);
+        for (uint64_t r = 0; r < nReads; r++) {
+            if ((uint64_t)b.id_off[r] + b.id_len[r] > b.text_bytes || (b.qual_off && (uint64_t)b.qual_off[r] + b.rlen[r] > b.text_bytes))
+                throw ArgError(std::string(who) + ": read " + std::to_string(r) + " has a place outside the text");
+            hw[r + 1] = hw[r] + (((uint64_t)b.rlen[r] + 31) >> 5);
+        }
+        nWords = hw[nReads];
+        put(text, b.text, b.text_bytes, kTextPad, 0);
+        put(idOff, b.id_off, nReads, 16, kTapFill); put(idLen, b.id_len, nReads, 16, kTapFill); put(rlen, b.rlen, nReads, 16, kTapFill);
+        if (b.qual_off) put(qualOff, b.qual_off, nReads, 16, kTapFill);
+        put(bases, b.bases, nWords, kBatchWordPad, kTapFill); put(nmask, b.nmask, nWords, kBatchWordPad, kTapFill);
+        put(qinfo, b.qinfo, nq, 16, kTapFill);
+        woff.upload(hw);
+    }
+};
+}  // extern "C++"
+// the places of a string table: n + 1 of them, none before its predecessor, none beyond the strings
+static void tapTable(const uint32_t *off, uint64_t n, uint64_t bytes, const char *what) {
+    if (!off) throw ArgError(std::string("cf_debug_format: no ") + what);
+    for (uint64_t i = 0; i <= n; i++)
+        if (off[i] > bytes || (i && off[i] < off[i - 1])) throw ArgError(std::string("cf_debug_format: ") + what + " is no table of places in its strings");
+}
+
+cf_status cf_debug_format(int device, const cf_debug_format_in *in, cf_debug_format_out *out) {
+    if (!in || !out || !out->text || !out->size || !out->single || !out->tuples) return CF_ERR_ARG;
+    if (in->n_cols > kTextMaxCols) { g_err = "cf_debug_format: a row has up to 32 columns"; return CF_ERR_ARG; }
+    if (in->n_cols && !in->cols) return CF_ERR_ARG;
+    for (uint32_t i = 0; i < in->n_cols; i++) if (in->cols[i] >= kColCount) { g_err = "cf_debug_format: column " + std::to_string(i) + " is none of the formatter's"; return CF_ERR_ARG; }
+    out->total = 0; out->tuple_words = 0;
+    std::memset(out->single, 0, ((size_t)in->n_taxa + 1) * 8);
+    if (in->block.n_queries == 0) return CF_OK;
+    if (!haveDevice()) return CF_ERR_NO_DEVICE;
+    return guard([&] {
+        HIP_OK(hipSetDevice(device));
+        const cf_debug_block &b = in->block;
+        const uint64_t nq = b.n_queries;
+        if (!in->rows || !in->score2 || !in->max_score || !in->strs || !in->tax_leaf) throw ArgError("cf_debug_format: a null array");
+        if (in->idx_zero > in->n_taxa) throw ArgError("cf_debug_format: idx_zero is a dense taxon, or n_taxa");
+        tapTable(in->uid_off, in->n_refs, in->strs_bytes, "uid_off"); tapTable(in->rank_off, in->n_taxa, in->strs_bytes, "rank_off");
+        tapTable(in->tax_off, in->n_taxa, in->strs_bytes, "tax_off");
+        TextCols pc{};
+        bool needTax = false;
+        for (uint32_t i = 0; i < in->n_cols; i++) { pc.col[i] = in->cols[i]; needTax = needTax || pc.col[i] == kColTaxRank || pc.col[i] == kColTaxName; }
+        pc.nCols = in->n_cols;
+        if (needTax) {
+            if (!in->tax_strs) throw ArgError("cf_debug_format: no tax_strs");
+            tapTable(in->trank_off, (uint64_t)in->n_taxa + 1, in->tax_strs_bytes, "trank_off"); tapTable(in->tname_off, (uint64_t)in->n_taxa + 1, in->tax_strs_bytes, "tname_off");
+        }
+        // rowFirst as the row stage's scan leaves it: the exclusive sums of the queries' rows
+        std::vector<uint64_t> rowFirst(nq + 1, 0);
+        for (uint64_t q = 0; q < nq; q++) rowFirst[q + 1] = rowFirst[q] + (b.qinfo[q] & 0x3fu);
+        const uint64_t nRows = rowFirst[nq];
+        TapBlock blk;
+        blk.make(b, "cf_debug_format");
+        DevBuf<TextRow> rows; DevBuf<uint32_t> score2, maxScore, uidOff, rankOff, taxOff, trankOff, tnameOff, tileC; DevBuf<uint64_t> dRowFirst, tileA;
+        DevBuf<uint8_t> strs, taxLeaf, taxStrs; DevBuf<TextStatus> st;
+        TapBlock::put(rows, reinterpret_cast<const TextRow *>(in->rows), nRows, 1, kTapFill);
+        TapBlock::put(score2, in->score2, nq, 1, kTapFill); TapBlock::put(maxScore, in->max_score, nq, 1, kTapFill);
+        dRowFirst.upload(rowFirst);
+        TapBlock::put(strs, in->strs, in->strs_bytes, 0, 0); TapBlock::put(taxLeaf, in->tax_leaf, in->n_taxa, 0, 0);
+        TapBlock::put(uidOff, in->uid_off, (uint64_t)in->n_refs + 1, 0, 0); TapBlock::put(rankOff, in->rank_off, (uint64_t)in->n_taxa + 1, 0, 0);
+        TapBlock::put(taxOff, in->tax_off, (uint64_t)in->n_taxa + 1, 0, 0);
+        if (needTax) {
+            TapBlock::put(taxStrs, in->tax_strs, in->tax_strs_bytes, 0, 0);
+            TapBlock::put(trankOff, in->trank_off, (uint64_t)in->n_taxa + 2, 0, 0); TapBlock::put(tnameOff, in->tname_off, (uint64_t)in->n_taxa + 2, 0, 0);
+        }
+        st.alloc(1); tileA.alloc(scan_tiles_for(nq) + 1); tileC.alloc(scan_tiles_for(nq) + 1);
+        HIP_OK(hipMemset(st.p, 0, sizeof(TextStatus)));
+        TapBuf text, size, outOff, tuples, single;
+        text.make(in->out_cap, kTapUnwritten); size.make(nq * 4, kTapUnwritten); outOff.make((nq + 1) * 8, kTapUnwritten);
+        tuples.make((uint64_t)in->tuples_cap * 4, kTapUnwritten); single.make(((uint64_t)in->n_taxa + 1) * 8, 0);
+        PinBuf<uint64_t> hTotal; hTotal.ensure(1);
+        DTextFmt f{};
+        f.text = blk.text.p; f.idOff = blk.idOff.p; f.idLen = blk.idLen.p; f.rlen = blk.rlen.p;
+        f.rows = rows.p; f.rowFirst = dRowFirst.p; f.qinfo = blk.qinfo.p; f.score2 = score2.p; f.maxScore = maxScore.p;
+        f.nQueries = (uint32_t)nq; f.paired = b.paired ? 1u : 0u;
+        f.strs = strs.p; f.uidOff = uidOff.p; f.rankOff = rankOff.p; f.taxOff = taxOff.p; f.taxLeaf = taxLeaf.p;
+        f.nRefs = in->n_refs; f.nTaxa = in->n_taxa; f.idxZero = in->idx_zero;
+        f.size = reinterpret_cast<uint32_t *>(size.p); f.single = reinterpret_cast<unsigned long long *>(single.p);
+        f.tuples = reinterpret_cast<uint32_t *>(tuples.p); f.tuplesCap = in->tuples_cap; f.st = st.p;
+        if (pc.nCols) {
+            if (needTax) { f.taxStrs = taxStrs.p; f.trankOff = trankOff.p; f.tnameOff = tnameOff.p; }
+            f.woff = blk.woff.p; f.bases = blk.bases.p; f.nmask = blk.nmask.p; f.qualOff = b.qual_off ? blk.qualOff.p : nullptr;
+        }
+        out->total = enqueueFormat(f, pc, reinterpret_cast<uint64_t *>(outOff.p), tileA.p, tileC.p, hTotal.p, nullptr,
+                                   [&](uint64_t) { f.out = text.p; f.outCap = in->out_cap; });
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipGetLastError());
+        text.check("the text"); size.check("the sizes"); outOff.check("the sizes' sums"); tuples.check("the tuples"); single.check("the single assignments");
+        TextStatus hs;
+        HIP_OK(hipMemcpy(&hs, st.p, sizeof hs, hipMemcpyDeviceToHost));
+        if (hs.outBytes != out->total) throw std::logic_error("cf_debug_format: the write pass reports other bytes than the size pass summed");
+        out->tuple_words = hs.tupleWords;
+        if (in->out_cap) HIP_OK(hipMemcpy(out->text, text.p, in->out_cap, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(out->size, size.p, nq * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(out->single, single.p, ((size_t)in->n_taxa + 1) * 8, hipMemcpyDeviceToHost));
+        if (in->tuples_cap) HIP_OK(hipMemcpy(out->tuples, tuples.p, (size_t)in->tuples_cap * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+cf_status cf_debug_split(int device, const cf_debug_block *block, uint32_t sinks, cf_debug_split_out *out) {
+    if (!block || !out) return CF_ERR_ARG;
+    if (sinks & ~(CF_SPLIT_UN | CF_SPLIT_AL)) { g_err = "cf_debug_split: sinks is CF_SPLIT_UN | CF_SPLIT_AL or 0"; return CF_ERR_ARG; }
+    const uint32_t mask = splitSinkMask(sinks, block->paired != 0);
+    for (uint32_t s = 0; s < kSplitSinks; s++) {
+        out->bytes[s] = out->records[s] = 0; out->sized[s] = mask >> s & 1u;
+        if (out->sized[s] && out->cap[s] && !out->text[s]) return CF_ERR_ARG;
+    }
+    if (block->n_queries == 0) return CF_OK;
+    if (!haveDevice()) return CF_ERR_NO_DEVICE;
+    return guard([&] {
+        HIP_OK(hipSetDevice(device));
+        const uint64_t nq = block->n_queries;
+        TapBlock blk;
+        blk.make(*block, "cf_debug_split");
+        DTextSplit d{};
+        d.text = blk.text.p; d.idOff = blk.idOff.p; d.idLen = blk.idLen.p; d.rlen = blk.rlen.p; d.qinfo = blk.qinfo.p;
+        d.woff = blk.woff.p; d.bases = blk.bases.p; d.nmask = blk.nmask.p; d.qualOff = block->qual_off ? blk.qualOff.p : nullptr;
+        d.nQueries = (uint32_t)nq; d.paired = block->paired ? 1u : 0u; d.sinks = sinks;
+        TapBuf size[kSplitSinks], offs[kSplitSinks], text[kSplitSinks], rec;
+        uint64_t *off[kSplitSinks] = {};
+        rec.make(kSplitSinks * 8, kTapUnwritten);
+        d.nRec = reinterpret_cast<unsigned long long *>(rec.p);
+        for (uint32_t s = 0; s < kSplitSinks; s++) {
+            if (!(mask >> s & 1u)) continue;
+            size[s].make(nq * 4, kTapUnwritten); offs[s].make((nq + 1) * 8, kTapUnwritten); text[s].make(out->cap[s], kTapUnwritten);
+            d.size[s] = reinterpret_cast<uint32_t *>(size[s].p); off[s] = reinterpret_cast<uint64_t *>(offs[s].p);
+        }
+        DevBuf<uint64_t> tileA; DevBuf<uint32_t> tileC;
+        tileA.alloc(scan_tiles_for(nq) + 1); tileC.alloc(scan_tiles_for(nq) + 1);
+        PinBuf<uint64_t> tot; tot.ensure(2 * kSplitSinks);
+        std::memset(tot.p, 0, 2 * kSplitSinks * 8);
+        enqueueSplit(d, mask, off, tileA.p, tileC.p, tot.p, nullptr, nullptr, [&](const uint64_t *) {
+            for (uint32_t s = 0; s < kSplitSinks; s++) if (mask >> s & 1u) { d.out[s] = text[s].p; d.cap[s] = out->cap[s]; }
+        });
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipGetLastError());
+        rec.check("the records' tally");
+        static const char *const kWhat[3][kSplitSinks] = {{"sink 0's sizes", "sink 1's sizes", "sink 2's sizes", "sink 3's sizes"},
+                                                          {"sink 0's sums", "sink 1's sums", "sink 2's sums", "sink 3's sums"},
+                                                          {"sink 0's text", "sink 1's text", "sink 2's text", "sink 3's text"}};
+        for (uint32_t s = 0; s < kSplitSinks; s++) {
+            if (!(mask >> s & 1u)) continue;
+            size[s].check(kWhat[0][s]); offs[s].check(kWhat[1][s]); text[s].check(kWhat[2][s]);
+            out->bytes[s] = tot.p[s]; out->records[s] = tot.p[kSplitSinks + s];
+            if (out->cap[s]) HIP_OK(hipMemcpy(out->text[s], text[s].p, out->cap[s], hipMemcpyDeviceToHost));
         }
     });
 }

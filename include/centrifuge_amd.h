@@ -713,6 +713,65 @@ cf_status cf_debug_inflate(int device, int by_lane, const void *members, uint64_
                            uint8_t *text, uint32_t *status, uint32_t *blocks, uint64_t *n_members, uint64_t *text_bytes, int64_t *bad_member);
 cf_status cf_debug_deflate(int device, const void *text, uint64_t n_bytes, uint32_t member, uint8_t *out, uint64_t out_cap,
                            uint64_t *out_bytes, uint32_t *sizes, uint64_t sizes_cap, uint64_t *n_members);
+/* The egress stage on its own: the formatter (fmt_size_body / fmt_write_body, or with n_cols > 0 fmt_cols_size_body /
+ * fmt_cols_write_body) and the read splitter (split_size_body / split_write_body), launched by the code cf_batch_wait_text and
+ * cf_batch_wait_text_split launch them with, on what the caller says a batch left on the device.  No index, classifier or slot;
+ * nothing is kept between calls.  Every device buffer the kernels write lies between filled margins of 256 bytes that are read
+ * back: a changed margin byte fails the call (cf_last_error names the margin).  The inputs get the room a slot gives them: 128
+ * zero bytes behind the text, 16 words behind the packed reads.
+ * cf_debug_block: the uploaded text (the places count from its first byte), per read — n_queries of them, twice as many with
+ * paired — where its readID lies, its length and, FASTQ, where its qualities lie (qual_off NULL: FASTA); the reads' 2-bit words
+ * and N masks one behind the other, ceil(rlen / 32) each; per query its byte of the narrow results (the rows in its low six bits).
+ * The taps check that every place lies inside the text and every table inside its strings (CF_ERR_ARG).
+ * cf_debug_format: rows — 16 bytes each: uniqueID, dense taxon, score, hitLength; a query's rows behind those of the queries
+ * before it —, score2 and max_score per query, and the string tables of cf_textio.hpp's DTextFmt (uid_off: n_refs + 1 places in
+ * strs, rank_off and tax_off: n_taxa + 1; trank_off and tname_off: n_taxa + 2 places in tax_strs, needed when a column asks for
+ * them).  cols: n_cols CF_COL_* codes, 0: the default eight; more than 32, or a code that is none, is CF_ERR_ARG.
+ * Out: text (out_cap bytes: rows that do not fit the room are left out, 0x5A where nothing was written), size (a word per
+ * query), single (n_taxa + 1 words, the perfect single assignments per dense taxon), tuples (tuples_cap words; the tuples that
+ * fit) with *tuple_words the words all tuples need, *total the bytes the size pass summed.  n_queries == 0: nothing is launched.
+ * cf_debug_split: sinks (CF_SPLIT_UN | CF_SPLIT_AL) and a room per sink -> per sink its text (cap[s] bytes, 0x5A where nothing was
+ * written), the bytes sized, the records and whether it was sized at all. */
+typedef struct {
+    const uint8_t  *text;
+    uint64_t        text_bytes;
+    const uint32_t *id_off, *id_len, *rlen, *qual_off;
+    const uint64_t *bases;
+    const uint32_t *nmask;
+    const uint8_t  *qinfo;
+    uint32_t        n_queries, paired;
+} cf_debug_block;
+typedef struct {
+    cf_debug_block  block;
+    const uint32_t *rows, *score2, *max_score;
+    const uint8_t  *strs;
+    uint64_t        strs_bytes;
+    const uint32_t *uid_off, *rank_off, *tax_off;
+    const uint8_t  *tax_leaf;
+    uint32_t        n_refs, n_taxa, idx_zero, n_cols;
+    const uint8_t  *tax_strs;
+    uint64_t        tax_strs_bytes;
+    const uint32_t *trank_off, *tname_off;
+    const uint8_t  *cols;
+    uint64_t        out_cap;
+    uint32_t        tuples_cap, reserved_;
+} cf_debug_format_in;
+typedef struct {
+    uint8_t  *text;
+    uint32_t *size;
+    uint64_t *single;
+    uint32_t *tuples;
+    uint64_t  total;
+    uint32_t  tuple_words, reserved_;
+} cf_debug_format_out;
+typedef struct {
+    uint8_t *text[4];
+    uint64_t cap[4];
+    uint64_t bytes[4], records[4];
+    uint32_t sized[4];
+} cf_debug_split_out;
+cf_status cf_debug_format(int device, const cf_debug_format_in *in, cf_debug_format_out *out);
+cf_status cf_debug_split(int device, const cf_debug_block *block, uint32_t sinks, cf_debug_split_out *out);
 /* random 128-byte-side read bandwidth of the device over the resident sides
  * (the roofline denominator of SURVEY.md §8d): GB/s over `n_loads` loads. */
 cf_status cf_debug_random_read_gbps(cf_index *, uint64_t n_loads, int dependent_steps, double *gbps);

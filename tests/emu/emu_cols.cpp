@@ -138,9 +138,10 @@ struct EmuColsIn {
     unsigned long long *single;           // per taxon: added to
     uint32_t *tuples;
     uint32_t *tupleWords;
+    uint32_t *size;                       // per query: what the size pass left
 };
-// returns the bytes of text (out holds outCap of them; rows that do not fit are left out, as on the device); ~0: too many columns,
-// ~0 - 1: a byte behind the room was written
+// returns the bytes of text (out holds outCap of them; rows that do not fit are left out, as on the device, and a byte of the room
+// that nothing wrote is 0x5A); ~0: too many columns, ~0 - 1: a byte behind the room was written
 uint64_t emu_cols_format(const EmuColsIn *in) {
     const uint32_t nq = in->nQueries, nReads = in->paired ? 2 * nq : nq;
     std::vector<uint64_t> rowFirst(nq + 1, 0), outOff(nq + 1, 0), woff(nReads + 1, 0);
@@ -149,6 +150,7 @@ uint64_t emu_cols_format(const EmuColsIn *in) {
     // (the output starts on a dword boundary, as device memory does; behind the room it has: marked bytes that must stay as they are)
     const size_t outWords = (size_t)(in->outCap / 4 + 2), guardWords = 64;
     std::vector<uint32_t> size(nq + 1, 0), outBuf(outWords + guardWords, 0);
+    std::memset(outBuf.data(), 0x5A, (size_t)in->outCap);
     std::memset(reinterpret_cast<uint8_t *>(outBuf.data()) + in->outCap, 0xA5, outBuf.size() * 4 - (size_t)in->outCap);
     TextStatus st{};
     DTextFmt f{};
@@ -179,7 +181,8 @@ uint64_t emu_cols_format(const EmuColsIn *in) {
     *in->tupleWords = st.tupleWords;
     const uint64_t total = nq ? st.outBytes : 0;
     for (size_t i = (size_t)in->outCap; i < outBuf.size() * 4; i++) if (reinterpret_cast<const uint8_t *>(outBuf.data())[i] != 0xA5) return ~0ull - 1;
-    std::memcpy(in->out, outBuf.data(), (size_t)(total < in->outCap ? total : in->outCap));
+    std::memcpy(in->out, outBuf.data(), (size_t)in->outCap);
+    for (uint32_t q = 0; q < nq; q++) in->size[q] = size[q];
     return total;
 }
 }  // extern "C"

@@ -41,7 +41,7 @@ class ColsIn(C.Structure):
                 ("nRefs", C.c_uint32), ("nTaxa", C.c_uint32), ("idxZero", C.c_uint32), ("nCols", C.c_uint32),
                 ("taxStrs", C.c_void_p), ("trankOff", C.c_void_p), ("tnameOff", C.c_void_p), ("cols", C.c_void_p),
                 ("defaultBodies", C.c_uint32), ("tuplesCap", C.c_uint32),
-                ("out", C.c_void_p), ("outCap", C.c_uint64), ("single", C.c_void_p), ("tuples", C.c_void_p), ("tupleWords", C.c_void_p)]
+                ("out", C.c_void_p), ("outCap", C.c_uint64), ("single", C.c_void_p), ("tuples", C.c_void_p), ("tupleWords", C.c_void_p), ("size", C.c_void_p)]
 
 
 def lib(wave64=False):
@@ -56,9 +56,20 @@ def lib(wave64=False):
     return _libs[wave64]
 
 
+UNWRITTEN = 0x5A       # what a byte of the room holds that no body wrote
+
+
 def format_rows(world, batch, cols, wave64=False, default_bodies=False, out_cap=None):
     """world: the string tables (dict of arrays), batch: the block and what the kernels left per read / query (dict of arrays);
     cols: column codes.  -> text (bytes), singles (u64 per taxon), tuples (u32 words)"""
+    text, _, n, single, tuples, _ = format_full(world, batch, cols, wave64, default_bodies, out_cap)
+    return text[:n], single, tuples
+
+
+def format_full(world, batch, cols, wave64=False, default_bodies=False, out_cap=None, tuples_cap=None):
+    """as format_rows, with what capi.debug_format gives for the device -> the room's out_cap bytes (UNWRITTEN where nothing was
+    written), the bytes per query, the bytes the size pass summed, singles, the tuple words that fit tuples_cap, the words all
+    tuples need"""
     L = lib(wave64)
     keep = []
 
@@ -89,11 +100,14 @@ def format_rows(world, batch, cols, wave64=False, default_bodies=False, out_cap=
     cap = int(out_cap if out_cap is not None else batch["outCap"])
     out = np.zeros(cap + 16, dtype=np.uint8)
     single = np.zeros(world["nTaxa"] + 1, dtype=np.uint64)
-    tcap = nq * 64 + 16
-    tuples = np.zeros(tcap, dtype=np.uint32)
+    tcap = nq * 64 + 16 if tuples_cap is None else int(tuples_cap)
+    tuples = np.full(tcap + 16, 0x5A5A5A5A, dtype=np.uint32)
+    size = np.zeros(nq + 1, dtype=np.uint32)
+    x.size = size.ctypes.data
     tw = C.c_uint32(0)
     x.tuplesCap, x.out, x.outCap, x.single, x.tuples, x.tupleWords = tcap, out.ctypes.data, cap, single.ctypes.data, tuples.ctypes.data, C.addressof(tw)
     n = L.emu_cols_format(C.byref(x))
     assert n != 2 ** 64 - 1, "more columns than the kernels take"
     assert n != 2 ** 64 - 2, "the write pass wrote past the room it was given"
-    return out[:min(n, cap)].tobytes(), single, tuples[:tw.value].copy()
+    assert np.all(tuples[tcap:] == 0x5A5A5A5A), "the write pass wrote a tuple behind the room it was given"
+    return out[:cap].tobytes(), size[:nq].copy(), int(n), single, tuples[:min(tw.value, tcap)].copy(), int(tw.value)

@@ -158,6 +158,7 @@ int emu_split_run(EmuSplitIn *in) {
         const uint64_t cap = in->bytes[s] < in->outCap[s] ? in->bytes[s] : in->outCap[s];
         buf[s].assign((size_t)(cap / 4 + 2) + 2 * guard / 4, 0xA5A5A5A5u);
         d.out[s] = reinterpret_cast<uint8_t *>(buf[s].data()) + guard; d.cap[s] = cap;
+        std::memset(d.out[s], 0x5A, (size_t)cap);                      // (a byte of the room that nothing wrote)
     }
     emuThreads((uint64_t)nq + 70, [&](uint32_t q) { split_write_body(d, q); });
     int bad = 0;

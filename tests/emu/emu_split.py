@@ -51,6 +51,9 @@ def lib(wave64=False):
     return _libs[wave64]
 
 
+UNWRITTEN = 0x5A       # what a byte of a sink's room holds that no body wrote
+
+
 def split(batch, sinks, wave64=False, cap=1 << 22):
     """batch: the block and what the kernels left per read / query (dict of arrays, as emu_cols.format_rows takes it); sinks: the
     CF_SPLIT_* bits.  -> per sink (text, bytes the size pass counted, records, sized)"""
@@ -72,10 +75,11 @@ def split(batch, sinks, wave64=False, cap=1 << 22):
     x.bases, x.nmask = arr(np.append(batch["bases"], np.zeros(2, np.uint64)), np.uint64), arr(np.append(batch["nmask"], np.zeros(2, np.uint32)), np.uint32)
     x.qinfo = arr(batch["qinfo"], np.uint8)
     x.nQueries, x.paired, x.sinks = len(batch["qinfo"]), int(batch["paired"]), int(sinks)
-    outs = [np.zeros(cap + 16, dtype=np.uint8) for _ in range(4)]
+    caps = [int(cap)] * 4 if np.isscalar(cap) else [int(c) for c in cap]
+    outs = [np.zeros(c + 16, dtype=np.uint8) for c in caps]
     for s in range(4):
         x.out[s] = outs[s].ctypes.data
-        x.outCap[s] = cap
+        x.outCap[s] = caps[s]
     bad = L.emu_split_run(C.byref(x))
     assert not bad, "the write pass wrote outside a sink's room"
-    return [(outs[s][:min(x.bytes[s], cap)].tobytes(), int(x.bytes[s]), int(x.records[s]), bool(x.sized[s])) for s in range(4)]
+    return [(outs[s][:min(x.bytes[s], caps[s])].tobytes(), int(x.bytes[s]), int(x.records[s]), bool(x.sized[s])) for s in range(4)]
