@@ -2569,9 +2569,10 @@ cf_status cf_batch_set_text_columns(cf_batch *bt, const int32_t *cols, uint32_t 
         pc.col[i] = (uint8_t)cols[i];
     }
     pc.nCols = nCols;
-    // the default eight, spelled out, are the default program: the default kernels print them
-    static const uint8_t kDefault[8] = {kColReadId, kColSeqId, kColTaxId, kColScore, kColScore2, kColHitLen, kColQueryLen, kColNumMatches};
-    if (nCols == 8 && !std::memcmp(pc.col, kDefault, 8)) pc = TextCols{};
+    // the default eight, spelled out, are the default program (FmtDefaultCols): the default kernels print them
+    bool isDefault = nCols == FmtDefaultCols::nCols();
+    for (uint32_t i = 0; i < nCols && isDefault; i++) isDefault = pc.col[i] == FmtDefaultCols::col(i);
+    if (isDefault) pc = TextCols{};
     bt->textCols = pc;
     return CF_OK;
 }
@@ -2612,7 +2613,8 @@ static void enqueueDeflate(uint8_t *text, uint64_t nBytes, uint32_t member, uint
     HIP_OK(hipMemcpyAsync(hTotal, zOff + nMembers, 8, hipMemcpyDeviceToHost, st));
 }
 
-// The text of a batch's rows (cf_textio.hpp "egress"), on st: the size pass — pc.nCols == 0: the default eight's bodies —, the
+// The text of a batch's rows (cf_textio.hpp "egress"), on st: the size pass — one pair of bodies, fmt_rows_size / fmt_rows_write, in
+// two kernels each: pc.nCols == 0 launches the ones compiled for the default eight, a list the ones that read it —, the
 // exclusive sums of the sizes into outOff[0 .. nQueries], their total fetched through *hTotal and WAITED for; room(total) then
 // names f.out and f.outCap, and the write pass is queued behind it.  Blocks of 256 threads: fmt_wave_lds keeps a stage per
 // wavefront of such a block.  f.nQueries > 0; returns the total.  (cf_batch_wait_text and cf_debug_format)

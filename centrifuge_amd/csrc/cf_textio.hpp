@@ -19,9 +19,9 @@
 //          sequence, every character of it >= 33.  A 3-field record r is read r - skip of the batch, a pair record reads
 //          2 (r - skip) and 2 (r - skip) + 1; under TAB5 the second mate's readID is the first's; a mate's seed starts from seed0
 //          with its own name, bases and qualities; trim5 / trim3 window each mate's fields as they window a FASTQ record's lines.
-// Egress: the default eight columns of AlnSinkSam::appendMate — or any other list of its columns (fmt_cols_*_body, at the end) — (aln_sink.h:2279-2337; centrifuge.cpp:520) are formatted here from
-// the narrow rows the batch leaves on the device, the readID copied out of the uploaded block (aln_sink.h:2203-2217), into a
-// buffer the host only write()s; and the part of SpeciesMetrics (aln_sink.h:142-172) the per-taxon counters of count_body do not
+// Egress: the default eight columns of AlnSinkSam::appendMate — or any other list of its columns, by the same two bodies —
+// (aln_sink.h:2279-2337; centrifuge.cpp:520) are formatted here from the narrow rows the batch leaves on the device, the readID
+// copied out of the uploaded block (aln_sink.h:2203-2217), into a buffer the host only write()s; and the part of SpeciesMetrics (aln_sink.h:142-172) the per-taxon counters of count_body do not
 // hold — the perfect single assignments and the perfect multi-assignment tuples the EM runs on — is tallied by the same pass.
 //
 // Every body is one thread per item and runs in the CPU harness (tests/emu) as a plain loop; the cross-lane parts are sums only.
@@ -141,7 +141,7 @@ struct DTextRec {
     // mates: two blocks in one buffer (text = this block's first byte, textBase = its place in the buffer: the places left for the
     // later passes count from the buffer's start), record r of block `mate` is read stride * r + mate of the batch
     uint32_t textBase, stride, mate;
-    uint32_t *qualOff;           // FASTQ: first byte of the record's quality line (nullptr: not kept; the readQual columns of fmt_cols_write_body)
+    uint32_t *qualOff;           // FASTQ: first byte of the record's quality line (nullptr: not kept; the readQual columns of fmt_rows_write)
     // -5 / -3 / -s (cf_batch_set_text_trim, cf_batch_set_text_skip; all zero: none of it).  A read is the window of its record's
     // bases behind the first trim5 and in front of the last trim3 of them (pat.cpp: the parsers' trimming) — rlen, seeds, seqOff,
     // qualOff and the block's sums speak of the window, the plain-form checks of the whole record.  The block's first `skip`
@@ -556,9 +556,11 @@ CF_DEV void text_pack_body(const DTextPack &d, uint32_t r) {
     }
 }
 
-// ---- egress: the default columns
-//   readID seqID taxID score 2ndBestScore hitLength queryLength numMatches   (centrifuge.cpp:520; aln_sink.h:2279-2337)
-// one thread per query: fmt_size_body leaves the bytes its rows take, fmt_write_body (behind the exclusive sums) writes them.
+// ---- egress: a batch's rows as text.  The columns are a program: any list of the fields of AlnSinkSam::appendMate (--tab-fmt-cols,
+// --out-fmt sam: centrifuge.cpp:484-520; aln_sink.h:2279-2337), the default one being
+//   readID seqID taxID score 2ndBestScore hitLength queryLength numMatches   (centrifuge.cpp:520)
+// One thread per query: the size pass (fmt_rows_size) leaves the bytes its rows take, the write pass (fmt_rows_write, behind the
+// exclusive sums) writes them; fmt_col_len / fmt_col_put are the one place that knows a column's width and text.
 struct TextRow { uint32_t uniqueID, tidx, score, hitLen; };          // = NarrowRow
 struct DTextFmt {
     const uint8_t *text;
@@ -583,7 +585,7 @@ struct DTextFmt {
     uint32_t *tuples;
     uint32_t tuplesCap;
     TextStatus *st;
-    // what the columns beyond the default eight need (fmt_cols_size_body / fmt_cols_write_body; the default bodies read none of it):
+    // what the columns beyond the default eight need (the default program reads none of it, and for it all of this may be null):
     // per taxon its rank's and its name's string — nTaxa + 1 of each, the last one tax ID 0's, which an unclassified row prints —,
     // the batch's packed reads (readSeq is printed from them: the uploaded text may be wrapped or lower case), and per read the
     // place of its quality line in `text` (nullptr: FASTA, whose qualities are 'I' throughout)
@@ -604,134 +606,21 @@ CF_DEV uint8_t *tx_copy(uint8_t *w, const uint8_t *s, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) w[i] = s[i];
     return w + n;
 }
-CF_DEV void fmt_size_body(const DTextFmt &f, uint32_t q) {
-    if (q >= f.nQueries) return;
-    const uint32_t ra = f.paired ? 2 * q : q;
-    const uint32_t qlen = f.rlen[ra] + (f.paired ? f.rlen[ra + 1] : 0u);
-    const uint32_t n = f.qinfo[q] & 0x3fu, id = f.idLen[ra], s2 = f.score2[q];
-    // what every row of the query has: readID \t ... 2ndBestScore \t ... queryLength \t numMatches \n
-    const uint32_t common = id + 1 + tx_digits(s2) + 1 + tx_digits(qlen) + 1 + tx_digits(n ? n : 1u) + 1;
-    uint32_t total;
-    if (n == 0) total = common + 12 + 1 + 1 + 1 + 1 + 1 + 1 + 1;       // unclassified \t 0 \t 0 \t [score2 \t] 0 \t
-    else {
-        total = n * common;
-        const uint64_t f0 = f.rowFirst[q];
-        for (uint32_t i = 0; i < n; i++) {
-            const TextRow row = f.rows[f0 + i];
-            const uint32_t t = row.tidx < f.nTaxa ? row.tidx : 0u;
-            const bool viaUid = f.taxLeaf[t] && row.uniqueID < f.nRefs;
-            total += (viaUid ? f.uidOff[row.uniqueID + 1] - f.uidOff[row.uniqueID] : f.rankOff[t + 1] - f.rankOff[t]) + 1 +
-                     (f.taxOff[t + 1] - f.taxOff[t]) + 1 + tx_digits(row.score) + 1 + tx_digits(row.hitLen) + 1;
-        }
-    }
-    f.size[q] = total;
-}
-// lds: kFmtLds + 8 bytes of LDS of the thread's WAVEFRONT (or nullptr).  A lane writes its rows a byte at a time, its neighbour's rows
-// start ~41 bytes further on: straight to HBM that is one store instruction per byte and 64 scattered bytes per instruction.  The 64
-// queries of a wavefront print one contiguous stretch of the text, so the rows are put together in LDS — at the stretch's own phase
-// within a dword — and go out as whole aligned dwords, 256 bytes per store instruction (a stretch that does not fit goes the old way).
+// The write pass's lds: kFmtLds + 8 bytes of LDS of the thread's WAVEFRONT (or nullptr).  A lane writes its rows a byte at a time,
+// its neighbour's rows start ~41 bytes further on: straight to HBM that is one store instruction per byte and 64 scattered bytes per
+// instruction.  The 64 queries of a wavefront print one contiguous stretch of the text, so the rows are put together in LDS — at the
+// stretch's own phase within a dword — and go out as whole aligned dwords, 256 bytes per store instruction (a stretch that does not
+// fit goes the old way).
 constexpr uint32_t kFmtLds = 8192;
 #ifndef CF_HOST_EMU
 // (the kernel is launched in blocks of 256 threads: cf_device.hip k_fmt_write)
 CF_DEV uint8_t *fmt_wave_lds() { __shared__ __attribute__((aligned(16))) uint8_t lds[256 / CF_WAVE][kFmtLds + 16]; return lds[threadIdx.x / CF_WAVE]; }
 #endif
-CF_DEV void fmt_write_body(const DTextFmt &f, uint32_t q, uint8_t *lds = nullptr) {
-#ifndef CF_HOST_EMU
-    if (!lds) lds = fmt_wave_lds();
-#endif
-    const bool live = q < f.nQueries;
-    uint32_t oneTaxon = 0xffffffffu;                                     // the taxon this query is a perfect single assignment of
-    const uint32_t lane = cf_lane(), q0 = q - lane;
-    const uint32_t qe = q0 + CF_WAVE < f.nQueries ? q0 + CF_WAVE : f.nQueries;
-    const uint64_t segBegin = q0 < f.nQueries ? f.outOff[q0] : 0, segEnd = q0 < f.nQueries ? f.outOff[qe] : 0;
-    const uint32_t phase = (uint32_t)(segBegin & 3u);
-    const bool viaLds = lds != nullptr && segEnd > segBegin && segEnd - segBegin + phase <= kFmtLds && segEnd <= f.outCap;
-    if (live) {
-        const uint32_t ra = f.paired ? 2 * q : q;
-        const uint32_t qlen = f.rlen[ra] + (f.paired ? f.rlen[ra + 1] : 0u);
-        const uint32_t n = f.qinfo[q] & 0x3fu, idn = f.idLen[ra], s2 = f.score2[q], ms = f.maxScore[q];
-        const uint8_t *id = f.text + f.idOff[ra];
-        const uint64_t o = f.outOff[q];
-        if (o + f.size[q] <= f.outCap) {
-            uint8_t *w = viaLds ? lds + phase + (uint32_t)(o - segBegin) : f.out + o;
-            if (n == 0) {
-                w = tx_copy(w, id, idn);
-                const uint8_t kU[] = {'\t', 'u', 'n', 'c', 'l', 'a', 's', 's', 'i', 'f', 'i', 'e', 'd', '\t', '0', '\t', '0', '\t'};
-                for (uint32_t i = 0; i < sizeof kU; i++) *w++ = kU[i];
-                w = tx_put(w, s2);
-                *w++ = '\t'; *w++ = '0'; *w++ = '\t';
-                w = tx_put(w, qlen); *w++ = '\t';
-                *w++ = '1'; *w++ = '\n';
-            } else {
-                const uint64_t f0 = f.rowFirst[q];
-                for (uint32_t i = 0; i < n; i++) {
-                    const TextRow row = f.rows[f0 + i];
-                    const uint32_t t = row.tidx < f.nTaxa ? row.tidx : 0u;
-                    w = tx_copy(w, id, idn); *w++ = '\t';
-                    if (f.taxLeaf[t] && row.uniqueID < f.nRefs) w = tx_copy(w, f.strs + f.uidOff[row.uniqueID], f.uidOff[row.uniqueID + 1] - f.uidOff[row.uniqueID]);
-                    else w = tx_copy(w, f.strs + f.rankOff[t], f.rankOff[t + 1] - f.rankOff[t]);
-                    *w++ = '\t';
-                    w = tx_copy(w, f.strs + f.taxOff[t], f.taxOff[t + 1] - f.taxOff[t]); *w++ = '\t';
-                    w = tx_put(w, row.score); *w++ = '\t';
-                    w = tx_put(w, s2); *w++ = '\t';
-                    w = tx_put(w, row.hitLen); *w++ = '\t';
-                    w = tx_put(w, qlen); *w++ = '\t';
-                    w = tx_put(w, n); *w++ = '\n';
-                }
-            }
-        }
-        // SpeciesMetrics::addSpeciesCounts (aln_sink.h:142-172), the part the per-taxon counters do not hold: only perfect hits feed the EM
-        if (n == 0) oneTaxon = f.idxZero;
-        else {
-            const uint64_t f0 = f.rowFirst[q];
-            if (n == 1) { const TextRow row = f.rows[f0]; if (ms != 0xffffffffu && row.score >= ms && row.tidx < f.nTaxa) oneTaxon = row.tidx; }
-            else {
-                bool all = ms != 0xffffffffu;
-                for (uint32_t i = 0; i < n && all; i++) { const TextRow row = f.rows[f0 + i]; all = row.score >= ms && row.tidx < f.nTaxa; }
-                if (all) {
-                    const uint32_t at = cf_atomic_add(&f.st->tupleWords, n + 1);
-                    if (at + n + 1 <= f.tuplesCap) { f.tuples[at] = n; for (uint32_t i = 0; i < n; i++) f.tuples[at + 1 + i] = f.rows[f0 + i].tidx; }
-                }
-            }
-        }
-    }
-    if (viaLds) {
-        // every lane's rows are in LDS (the operations of a wavefront on its LDS retire in order; the fence keeps the compiler's
-        // hands off the order): out they go, dword j of the stretch by lane j mod 64
-        cf_compiler_fence();
-        const uint32_t total = phase + (uint32_t)(segEnd - segBegin);
-        uint8_t *const dst = f.out + (segBegin - phase);                  // a dword boundary of the output
-        for (uint32_t j = lane; 4 * j < total; j += CF_WAVE) {
-            const uint32_t lo = 4 * j, hi = lo + 4;
-            if (lo >= phase && hi <= total) {
-                uint32_t v;
-                __builtin_memcpy(&v, lds + lo, 4);
-                *reinterpret_cast<uint32_t *>(dst + lo) = v;
-            } else
-                for (uint32_t k = lo < phase ? phase : lo; k < (hi < total ? hi : total); k++) dst[k] = lds[k];
-        }
-        cf_compiler_fence();
-    }
-    // one atomic per taxon and wavefront: the lanes that name the same taxon as the lowest waiting lane are counted by it
-    bool waiting = oneTaxon != 0xffffffffu;
-    for (;;) {
-        const uint64_t w = cf_ballot(waiting);
-        if (!w) break;
-        const uint32_t lead = cf_shfl(oneTaxon, cf_ctz64(w));
-        const uint64_t same = cf_ballot(waiting && oneTaxon == lead);
-        if (waiting && oneTaxon == lead) {
-            if ((uint32_t)cf_ctz64(same) == cf_lane()) cf_atomic_add(&f.single[lead], (unsigned long long)cf_popc64(same));
-            waiting = false;
-        }
-    }
-    if (live && q + 1 == f.nQueries) f.st->outBytes = f.outOff[f.nQueries];
-}
 
-// ---- egress: any list of columns (--tab-fmt-cols, --out-fmt sam: centrifuge.cpp:484-520; the fields of AlnSinkSam::appendMate,
-// aln_sink.h:2279-2337).  The program — up to kTextMaxCols column codes — comes by value.  The short fields (names, numbers) are
-// printed lane by lane as in the default bodies; the LONG ones (readSeq*, readQual*: a read's length each) are not: a 150-base row
-// would be 150 one-byte stores per lane, scattered over the wavefront's stretch.  They are written by the WHOLE wavefront, one
-// field after the other, in aligned dwords — the sequence expanded from the batch's 2-bit words in registers, 16 bases per lane.
+// The columns.  The short fields (names, numbers) are printed lane by lane; the LONG ones (readSeq*, readQual*: a read's length
+// each) are not: a 150-base row would be 150 one-byte stores per lane, scattered over the wavefront's stretch.  They are written by
+// the WHOLE wavefront, one field after the other, in aligned dwords — the sequence expanded from the batch's 2-bit words in
+// registers, 16 bases per lane.
 constexpr uint32_t kTextMaxCols = 32;
 enum : uint32_t {
     kColReadId = 0, kColSeqId, kColTaxId, kColTaxRank, kColTaxName, kColScore, kColScore2, kColHitLen, kColQueryLen, kColNumMatches,
@@ -800,15 +689,35 @@ CF_DEV uint8_t *fmt_col_put(const DTextFmt &f, const FmtQuery &Q, uint32_t c, bo
         default: return w + fmt_long_len(f, Q, c);                   // a long column: left to the wavefront
     }
 }
-CF_DEV void fmt_cols_size_body(const DTextFmt &f, const TextCols &pc, uint32_t q) {
+// The program of the two passes, a template parameter in two forms.  FmtListCols: a list that came by value.  FmtDefaultCols: the
+// default eight, known to the compiler — the passes unroll their column loops for it (kUnroll), so fmt_col_len / fmt_col_put see
+// constant codes and their switches are gone; it has no long column, so the write pass's whole-wavefront part is gone as well, and
+// none of its columns reads what DTextFmt keeps for the others (taxStrs, trankOff, tnameOff, woff, bases, nmask, qualOff).
+struct FmtListCols {
+    const TextCols &pc;
+    static constexpr uint32_t kUnroll = 1;
+    CF_DEV uint32_t nCols() const { return pc.nCols; }
+    CF_DEV uint32_t col(uint32_t k) const { return pc.col[k]; }
+};
+struct FmtDefaultCols {
+    static constexpr uint32_t kUnroll = 8;
+    static constexpr uint32_t nCols() { return 8; }
+    static constexpr uint32_t col(uint32_t k) {
+        constexpr uint8_t kDefault[8] = {kColReadId, kColSeqId, kColTaxId, kColScore, kColScore2, kColHitLen, kColQueryLen, kColNumMatches};
+        return kDefault[k];
+    }
+};
+template <typename P>
+CF_DEV void fmt_rows_size(const DTextFmt &f, const P &p, uint32_t q) {
     if (q >= f.nQueries) return;
     const FmtQuery Q = fmt_query(f, q);
     const bool uncl = Q.n == 0;
     uint32_t total = 0;
     for (uint32_t i = 0; i < (uncl ? 1u : Q.n); i++) {
         const TextRow row = uncl ? TextRow{0, 0, 0, 0} : f.rows[Q.f0 + i];
-        total += pc.nCols;                                               // the tabs between the columns and the '\n'
-        for (uint32_t k = 0; k < pc.nCols; k++) total += fmt_col_len(f, Q, pc.col[k], uncl, row);
+        total += p.nCols();                                              // the tabs between the columns and the '\n'
+#pragma unroll P::kUnroll
+        for (uint32_t k = 0; k < p.nCols(); k++) total += fmt_col_len(f, Q, p.col(k), uncl, row);
     }
     f.size[q] = total;
 }
@@ -871,7 +780,8 @@ CF_DEV void fmt_wave_long(const DTextFmt &f, const FmtQuery &Q, uint32_t c, uint
         dst += n; at += n;
     }
 }
-CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t q, uint8_t *lds = nullptr) {
+template <typename P>
+CF_DEV void fmt_rows_write(const DTextFmt &f, const P &p, uint32_t q, uint8_t *lds) {
 #ifndef CF_HOST_EMU
     if (!lds) lds = fmt_wave_lds();
 #endif
@@ -882,8 +792,8 @@ CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t 
     const uint64_t segBegin = q0 < f.nQueries ? f.outOff[q0] : 0, segEnd = q0 < f.nQueries ? f.outOff[qe] : 0;
     const uint32_t phase = (uint32_t)(segBegin & 3u);
     const bool viaLds = lds != nullptr && segEnd > segBegin && segEnd - segBegin + phase <= kFmtLds && segEnd <= f.outCap;
-    bool anyLong = false;
-    for (uint32_t k = 0; k < pc.nCols; k++) anyLong = anyLong || tx_col_long(pc.col[k]);
+    bool anyLong = false;                                                // (the default program: false, known to the compiler)
+    for (uint32_t k = 0; k < p.nCols(); k++) anyLong = anyLong || tx_col_long(p.col(k));
     bool printed = false;
     if (live) {
         const FmtQuery Q = fmt_query(f, q);
@@ -895,10 +805,12 @@ CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t 
             uint8_t *w = viaLds ? lds + phase + (uint32_t)(o - segBegin) : f.out + o;
             for (uint32_t i = 0; i < (uncl ? 1u : Q.n); i++) {
                 const TextRow row = uncl ? TextRow{0, 0, 0, 0} : f.rows[Q.f0 + i];
-                for (uint32_t k = 0; k < pc.nCols; k++) { w = fmt_col_put(f, Q, pc.col[k], uncl, row, w); *w++ = k + 1 < pc.nCols ? '\t' : '\n'; }
+#pragma unroll P::kUnroll
+                for (uint32_t k = 0; k < p.nCols(); k++) { w = fmt_col_put(f, Q, p.col(k), uncl, row, w); *w++ = k + 1 < p.nCols() ? '\t' : '\n'; }
             }
         }
-        // SpeciesMetrics::addSpeciesCounts (aln_sink.h:142-172), as in fmt_write_body: the tally does not depend on the columns
+        // SpeciesMetrics::addSpeciesCounts (aln_sink.h:142-172), the part the per-taxon counters do not hold: only perfect hits feed
+        // the EM.  The tally does not depend on the columns
         if (uncl) oneTaxon = f.idxZero;
         else if (Q.n == 1) { const TextRow row = f.rows[Q.f0]; if (ms != 0xffffffffu && row.score >= ms && row.tidx < f.nTaxa) oneTaxon = row.tidx; }
         else {
@@ -922,8 +834,8 @@ CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t 
             uint64_t o = f.outOff[ql];
             for (uint32_t i = 0; i < (uncl ? 1u : Q.n); i++) {
                 const TextRow row = uncl ? TextRow{0, 0, 0, 0} : f.rows[Q.f0 + i];
-                for (uint32_t k = 0; k < pc.nCols; k++) {
-                    const uint32_t c = pc.col[k], n = fmt_col_len(f, Q, c, uncl, row);
+                for (uint32_t k = 0; k < p.nCols(); k++) {
+                    const uint32_t c = p.col(k), n = fmt_col_len(f, Q, c, uncl, row);
                     if (tx_col_long(c) && n) fmt_wave_long(f, Q, c, viaLds ? lds + phase + (uint32_t)(o - segBegin) : f.out + o, (uint32_t)(o & 3u), lane);
                     o += n + 1;
                 }
@@ -931,7 +843,8 @@ CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t 
         }
     }
     if (viaLds) {
-        // (as in fmt_write_body) every lane's bytes are in LDS: out they go, dword j of the stretch by lane j mod 64
+        // every lane's bytes are in LDS (the operations of a wavefront on its LDS retire in order; the fence keeps the compiler's
+        // hands off the order): out they go, dword j of the stretch by lane j mod 64
         cf_compiler_fence();
         const uint32_t total = phase + (uint32_t)(segEnd - segBegin);
         uint8_t *const dst = f.out + (segBegin - phase);                  // a dword boundary of the output
@@ -960,6 +873,11 @@ CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t 
     }
     if (live && q + 1 == f.nQueries) f.st->outBytes = f.outOff[f.nQueries];
 }
+// the bodies of the kernels: the default columns (k_fmt_size, k_fmt_write) and a list (k_fmt_cols_size, k_fmt_cols_write)
+CF_DEV void fmt_size_body(const DTextFmt &f, uint32_t q) { fmt_rows_size(f, FmtDefaultCols{}, q); }
+CF_DEV void fmt_write_body(const DTextFmt &f, uint32_t q, uint8_t *lds = nullptr) { fmt_rows_write(f, FmtDefaultCols{}, q, lds); }
+CF_DEV void fmt_cols_size_body(const DTextFmt &f, const TextCols &pc, uint32_t q) { fmt_rows_size(f, FmtListCols{pc}, q); }
+CF_DEV void fmt_cols_write_body(const DTextFmt &f, const TextCols &pc, uint32_t q, uint8_t *lds = nullptr) { fmt_rows_write(f, FmtListCols{pc}, q, lds); }
 
 // ---- egress: the reads themselves (--un / --al / --un-conc / --al-conc: the reference's wrapper script has centrifuge-class print
 // readSeq and readQual, cuts the two columns off again and writes a FASTQ record per ROW; here the records are made from what the

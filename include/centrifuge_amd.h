@@ -713,8 +713,8 @@ cf_status cf_debug_inflate(int device, int by_lane, const void *members, uint64_
                            uint8_t *text, uint32_t *status, uint32_t *blocks, uint64_t *n_members, uint64_t *text_bytes, int64_t *bad_member);
 cf_status cf_debug_deflate(int device, const void *text, uint64_t n_bytes, uint32_t member, uint8_t *out, uint64_t out_cap,
                            uint64_t *out_bytes, uint32_t *sizes, uint64_t sizes_cap, uint64_t *n_members);
-/* The egress stage on its own: the formatter (fmt_size_body / fmt_write_body, or with n_cols > 0 fmt_cols_size_body /
- * fmt_cols_write_body) and the read splitter (split_size_body / split_write_body), launched by the code cf_batch_wait_text and
+/* The egress stage on its own: the formatter (fmt_rows_size / fmt_rows_write: as fmt_size_body / fmt_write_body compiled for the
+ * default eight columns, or with n_cols > 0 as fmt_cols_size_body / fmt_cols_write_body reading the list) and the read splitter (split_size_body / split_write_body), launched by the code cf_batch_wait_text and
  * cf_batch_wait_text_split launch them with, on what the caller says a batch left on the device.  No index, classifier or slot;
  * nothing is kept between calls.  Every device buffer the kernels write lies between filled margins of 256 bytes that are read
  * back: a changed margin byte fails the call (cf_last_error names the margin).  The inputs get the room a slot gives them: 128
