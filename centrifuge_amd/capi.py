@@ -200,6 +200,7 @@ EXPORTS = [
     "cf_batch_upload_dense_async", "cf_batch_set_result_format", "cf_batch_wait_narrow", "cf_narrow_max_score", "cf_results_narrow_expand",
     "cf_build_input_default", "cf_build_index", "cf_build_timings", "cf_build_last_error", "cf_build_taxonomy", "cf_build_describe",
     "cf_debug_prim_scan", "cf_debug_inflate", "cf_debug_deflate", "cf_batch_debug_text_reads", "cf_debug_format", "cf_debug_split",
+    "cf_split_taxa_mask", "cf_classifier_set_split_taxa", "cf_batch_split_by_taxa", "cf_debug_split_taxa",
 ]
 
 _lib = None
@@ -296,6 +297,8 @@ def lib():
         "cf_batch_set_text_trim": (i32, [vp, u32, u32]), "cf_batch_set_text_skip": (i32, [vp, u64]),
         "cf_batch_set_text_split": (i32, [vp, u32, i32]), "cf_batch_wait_text_split": (i32, [vp, C.POINTER(SplitText)]),
         "cf_batch_split_ms": (i32, [vp, C.POINTER(C.c_float)]),
+        "cf_split_taxa_mask": (i32, [vp, vp, u64, vp, C.POINTER(u64)]), "cf_classifier_set_split_taxa": (i32, [vp, vp, u64, C.POINTER(u64)]),
+        "cf_batch_split_by_taxa": (i32, [vp, C.POINTER(C.c_int32)]), "cf_debug_split_taxa": (i32, [i32, vp, vp, vp, u32, u32, vp]),
         "cf_counts_get_single": (i32, [vp, vp]),
         "cf_report_add_tuples": (i32, [vp, vp, u64]), "cf_report_adopt_device_tally": (i32, [vp, vp, vp, vp, u64]),
         "cf_batch_set_limits": (i32, [vp, u64, u64]),
@@ -495,6 +498,15 @@ class Classifier:
         a, n = counts if counts is not None else self.kreport_counts()
         a = np.ascontiguousarray(a, dtype=np.uint64)
         _check(self.L.cf_kreport_write(self.index.h, a.ctypes.data, int(n), os.fsencode(path)))
+
+    def set_split_taxa(self, taxids):
+        """the taxa whose clades' rows the slots' later wait_text_split() calls write to the classified sinks, every other row to the
+        unclassified ones (cf_classifier_set_split_taxa; 0: the reads without an assignment; an empty list: no selection, the split
+        by "has an assignment" again).  -> the listed IDs the index does not know"""
+        a = np.ascontiguousarray(list(taxids), dtype=np.uint64)
+        n = C.c_uint64(0)
+        _check(self.L.cf_classifier_set_split_taxa(self.h, a.ctypes.data if len(a) else None, len(a), C.byref(n)))
+        return int(n.value)
 
     def allreduce_counts(self, nccl_comm, stream=None):
         """in-place RCCL sum of the device counters over the communicator's ranks"""
@@ -825,6 +837,12 @@ class Slot:
         _check(self.L.cf_batch_split_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def split_by_taxa(self):
+        """whether the last wait_text_split() sized its batch by a selection of taxa (cf_batch_split_by_taxa)"""
+        v = C.c_int32(0)
+        _check(self.L.cf_batch_split_by_taxa(self.h, C.byref(v)))
+        return bool(v.value)
+
     def kreport_ms(self):
         """k_kreport's time in the slot's last batch (cf_batch_kreport_ms)"""
         ms = C.c_float(0)
@@ -1152,6 +1170,30 @@ def debug_split(batch, sinks, cap=1 << 22, device=0):
         y.text[s], y.cap[s] = outs[s].ctypes.data, caps[s]
     _check(lib().cf_debug_split(device, C.byref(blk), int(sinks), C.byref(y)))
     return [(outs[s][:min(y.bytes[s], caps[s])].tobytes(), int(y.bytes[s]), int(y.records[s]), bool(y.sized[s])) for s in range(4)]
+
+
+def debug_split_taxa(batch, rows, mask, sinks, cap=1 << 22, device=0):
+    """debug_split with a selection of taxa (cf_debug_split_taxa): rows, four words each (uniqueID, dense taxon, score, hitLength),
+    a query's behind those of the queries before it; mask: a byte per dense taxon and one more for taxID 0.  -> as debug_split"""
+    keep = []
+    blk, arr = _debug_block(batch, keep)
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    caps = [int(cap)] * 4 if np.isscalar(cap) else [int(c) for c in cap]
+    y = DebugSplitOut()
+    outs = [np.zeros(c + 1, dtype=np.uint8) for c in caps]
+    for s in range(4):
+        y.text[s], y.cap[s] = outs[s].ctypes.data, caps[s]
+    _check(lib().cf_debug_split_taxa(device, C.byref(blk), arr(rows, np.uint32), mask.ctypes.data, len(mask) - 1, int(sinks), C.byref(y)))
+    return [(outs[s][:min(y.bytes[s], caps[s])].tobytes(), int(y.bytes[s]), int(y.records[s]), bool(y.sized[s])) for s in range(4)]
+
+
+def split_taxa_mask(index, taxids):
+    """--split-taxids' table (cf_split_taxa_mask; a host-only Index is enough): a byte per dense taxon of the index — 1: the taxon
+    or one of its ancestors is listed — and one more for taxID 0.  -> (mask, the listed IDs the index does not know)"""
+    a = np.ascontiguousarray(list(taxids), dtype=np.uint64)
+    mask, n = np.zeros(index.num_taxa + 1, dtype=np.uint8), C.c_uint64(0)
+    _check(lib().cf_split_taxa_mask(index.h, a.ctypes.data if len(a) else None, len(a), mask.ctypes.data, C.byref(n)))
+    return mask, int(n.value)
 
 
 class Report:

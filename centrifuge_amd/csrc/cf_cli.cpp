@@ -61,6 +61,9 @@ struct Opts {
     // --un / --al / --un-conc / --al-conc (and their -gz forms): where the reads themselves go, by what became of them (empty: nowhere)
     std::string splitPath[4];                           // un, al, un-conc, al-conc
     bool splitGz[4] = {false, false, false, false};
+    // --split-taxids: the taxa whose clades' ROWS go to the --al files, every other row to the --un files (not given: a row is `al` when its read has an assignment)
+    std::vector<uint64_t> splitTaxids;
+    bool splitTaxidsSet = false;
     bool hostIo = false;                                // --host-io: the parser pool and the formatter threads for every input (no device text path)
     int smallRangeRows = 0;                             // --small-range-rows: cf_index_options::small_range_rows (0 = automatic, -1 = off)
     double hbmBudgetGb = 0;                             // --hbm-budget-gb: cf_index_options::hbm_budget_bytes (0 = what the device has free)
@@ -111,6 +114,9 @@ void usage(std::FILE *f) {
         "          (the same for pairs, mate 1 and mate 2 in two files: every % of the name becomes 1 / 2, else x.fq becomes x.1.fq / x.2.fq,\n"
         "          else .1 / .2 is appended; a directory takes un-seqs, al-seqs, un-conc-mate.1 ...)  --un-gz --al-gz --un-conc-gz --al-conc-gz\n"
         "          (the same files as BGZF; blocks on the device text path are split and deflated there)\n"
+        "          --split-taxids <t,..> (with any of the above: the files are split by the ROW's taxID instead — a row whose taxID is one of\n"
+        "          <t,..> or lies below one of them in the index's taxonomy goes to the --al files, every other row to the --un files; 0\n"
+        "          selects the reads without an assignment; IDs the index does not know are named in a warning; the output does not change)\n"
         "          --out-bgzf (the classification output — -S or stdout: header line, rows, --separator markers, the SAM form — as one BGZF\n"
         "          file, the blocked gzip of bgzip / htslib, that inflates to the bytes the run prints without the flag; rows formatted on\n"
         "          the device are deflated there and cross the link compressed, the rest is deflated by zlib; the report stays plain)\n"
@@ -228,6 +234,15 @@ Opts parse(int argc, const char **argv) {
         else if (a == "--reorder" || a == "--mm" || a == "--non-deterministic" || a == "--qc-filter" || a == "--phred33" ||
                  a == "--ignore-quals" || a == "--nofw" || a == "--norc" || a == "--no-1mm-upfront") {}      // accepted, no effect on this path
         else if (a == "--min-totallen" || a == "--met-file" || a == "--met") (void)val();
+        else if (a == "--split-taxids") {
+            const std::vector<std::string> ids = splitComma(val());
+            if (ids.empty()) die("--split-taxids arg must be a comma-separated list of taxonomy IDs (0: the reads without an assignment)");
+            for (const auto &t : ids) {
+                if (t.size() > 19 || t.find_first_not_of("0123456789") != std::string::npos) die("--split-taxids: '" + t + "' is not a taxonomy ID");
+                o.splitTaxids.push_back(std::strtoull(t.c_str(), nullptr, 10));
+            }
+            o.splitTaxidsSet = true;
+        }
         else if (a.rfind("--un", 0) == 0 || a.rfind("--al", 0) == 0) {
             // centrifuge:212-227: --un / --al / --un-conc / --al-conc <path>, -gz: compressed (here: BGZF); -bz2 is not offered
             std::string k = a.substr(2);
@@ -262,6 +277,8 @@ Opts parse(int argc, const char **argv) {
                                                 std::to_string(o.mates2.size()) + " mate files/sequences were specified with -2.  The same number of mate files/sequences must be specified with -1 and -2.");
     if (o.minHitLen < 15) die("--min-hitlen arg must be at least 15");         // centrifuge.cpp:1402
     if (o.khits < 1) die("-k arg must be at least 1");
+    if (o.splitTaxidsSet && o.splitPath[0].empty() && o.splitPath[1].empty() && o.splitPath[2].empty() && o.splitPath[3].empty())
+        die("--split-taxids needs a file to split into: one of --un / --al / --un-conc / --al-conc (or their -gz forms)");
     (void)rankSlot(o.rank);                                                  // an unknown rank is an option error (centrifuge.cpp:1432-1445)
     if (o.upto + o.skip > o.upto) o.upto += o.skip;                          // -u counts after -s (centrifuge.cpp:1628-1633)
     for (const auto &c : o.colNames) o.cols.push_back(colOf(c));
@@ -840,6 +857,9 @@ struct Runner {
     };
     SplitFile sp[6];
     bool splitOn = false;
+    // --split-taxids: cf_split_taxa_mask's table (a byte per dense taxon, taxID 0's behind them) — what the classifiers hold on their
+    // devices, here for splitRange; empty: no selection
+    std::vector<uint8_t> splitMask;
     static int splitFileOf(bool paired, uint32_t sink) { return paired ? 2 + (int)sink : sink == 0 ? 0 : sink == 2 ? 1 : -1; }
     void splitOpen() {
         auto isDir = [](const std::string &p) { struct stat sb; return ::stat(p.c_str(), &sb) == 0 && S_ISDIR(sb.st_mode); };
@@ -912,16 +932,28 @@ struct Runner {
         std::string rec;
         for (uint64_t q = q0; q < q1; q++) {
             const size_t ra = q * per;
-            const uint32_t n = std::max<uint32_t>(1, nRows[q]), cls = nRows[q] ? 1u : 0u;
-            for (int m = 0; m < per; m++) {
-                const int f = b.paired ? 2 + 2 * (int)cls + m : (int)cls;
-                if (sp[f].fd < 0) continue;
+            // the records per class: all of them the read's, or with --split-taxids each row's own (split_sel_size_body's count)
+            uint32_t copies[2] = {nRows[q] ? 0u : 1u, nRows[q]};
+            if (!splitMask.empty()) {
+                const size_t nTaxa = splitMask.size() - 1;
+                uint32_t al = 0;
+                for (uint32_t i = 0; i < nRows[q]; i++) {
+                    const uint32_t t = b.narrowRows ? b.rows16[b.rowFirst[q] + i].taxon_idx : b.rows[b.rowFirst[q] + i].taxon_idx;
+                    al += splitMask[t < nTaxa ? t : 0] ? 1u : 0u;
+                }
+                if (!nRows[q]) al = splitMask[nTaxa] ? 1u : 0u;
+                copies[1] = al; copies[0] = std::max<uint32_t>(1, nRows[q]) - al;
+            }
+            for (int m = 0; m < 2 * per; m++) {
+                const uint32_t cls = (uint32_t)(m / per), n = copies[cls];
+                const int f = b.paired ? 2 + 2 * (int)cls + m % per : (int)cls;
+                if (sp[f].fd < 0 || !n) continue;
                 rec.assign(1, '@');
                 appendReadId(rec, r.names.data() + r.nameOff[ra], r.nameOff[ra + 1] - r.nameOff[ra]);
                 rec.push_back('\n');
-                appendSeq(rec, r, ra + m);
+                appendSeq(rec, r, ra + m % per);
                 rec += "\n+\n";
-                appendQual(rec, r, ra + m);
+                appendQual(rec, r, ra + m % per);
                 rec.push_back('\n');
                 for (uint32_t i = 0; i < n; i++) to[f] += rec;
             }
@@ -1603,6 +1635,21 @@ int run(int argc, const char **argv) {
         for (auto &d : R.devs) CF_TRY(cf_classifier_create(d.ix, &p, &d.clf));
         if (!o.kreportFile.empty())
             for (auto &d : R.devs) if (cf_kreport_enable(d.clf) != CF_OK) die(std::string("Error: --kreport-file: ") + cf_last_error());
+        if (o.splitTaxidsSet) {
+            // the selection on every device's classifier, and the same table here for the blocks the host splits; one list serves many
+            // indexes, so an ID this one does not know is a warning
+            const uint64_t nTaxa = cf_index_num_taxa(R.ix);
+            R.splitMask.assign(nTaxa + 1, 0);
+            if (cf_split_taxa_mask(R.ix, o.splitTaxids.data(), o.splitTaxids.size(), R.splitMask.data(), nullptr) != CF_OK) die(std::string("Error: --split-taxids: ") + cf_last_error());
+            for (auto &d : R.devs) if (cf_classifier_set_split_taxa(d.clf, o.splitTaxids.data(), o.splitTaxids.size(), nullptr) != CF_OK) die(std::string("Error: --split-taxids: ") + cf_last_error());
+            std::vector<uint64_t> taxa(nTaxa), seen;
+            for (uint64_t i = 0; i < nTaxa; i++) taxa[i] = cf_index_taxon_id(R.ix, i);
+            std::sort(taxa.begin(), taxa.end());
+            std::string unknown;
+            for (const uint64_t t : o.splitTaxids)
+                if (!std::binary_search(taxa.begin(), taxa.end(), t) && std::find(seen.begin(), seen.end(), t) == seen.end()) { seen.push_back(t); unknown += (unknown.empty() ? "" : ", ") + std::to_string(t); }
+            if (!unknown.empty()) std::fprintf(stderr, "Warning: --split-taxids: not in the index's taxonomy (no row is selected by them): %s\n", unknown.c_str());
+        }
         // The device text path (round 6): whole blocks of a plain FASTA / FASTQ file up as text, the rows back as text — with
         // -5 / -3 as the record pass's window (cf_batch_set_text_trim), -s / -u by the block (cf_batch_set_text_skip, max_reads), up to CF_TEXT_MAX_COLS columns (cf_batch_set_text_columns), -k <= 63 (the narrow rows' six bits).  Every GPU thread
         // then also reads its blocks and writes its text, so there are more of them (each with a slot on the device).

@@ -316,6 +316,7 @@ __global__ void __launch_bounds__(256) k_fmt_write(DTextFmt f) { fmt_write_body(
 __global__ void __launch_bounds__(256) k_fmt_cols_size(DTextFmt f, TextCols pc) { fmt_cols_size_body(f, pc, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_fmt_cols_write(DTextFmt f, TextCols pc) { fmt_cols_write_body(f, pc, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_split_size(DTextSplit d) { split_size_body(d, cf_global_thread()); }
+__global__ void __launch_bounds__(256) k_split_sel_size(DTextSplit d, DTextSplitSel e) { split_sel_size_body(d, e, cf_global_thread()); }
 __global__ void __launch_bounds__(256) k_split_write(DTextSplit d) { split_write_body(d, cf_global_thread()); }
 template <int G, bool WRITE>
 __global__ void __launch_bounds__(256) k_restore(DIndex ix, DRestore r) { restore_body<G, WRITE>(ix, r); }
@@ -437,6 +438,9 @@ struct cf_classifier {
     DevBuf<uint32_t> fmtTrankOff, fmtTnameOff;
     bool fmtTaxMade = false;
     std::mutex fmtMu;
+    // cf_classifier_set_split_taxa: the selection the slots' reads are split by (a byte per dense taxon + taxID 0's), or none
+    DevBuf<uint8_t> splitMask;
+    bool splitSel = false;
 };
 
 // pinned host memory that frees itself (results a batch hands back, staging of the byte input)
@@ -530,6 +534,7 @@ struct cf_batch {
     // sums, their text (or members) on the device and in pinned memory
     uint32_t splitSinks = 0;
     bool splitBgzf = false, splitDone = false;
+    bool splitByTaxa = false;                // the batch's split was sized by k_split_sel_size (cf_batch_split_by_taxa)
     DevBuf<uint32_t> spSize[kSplitSinks];
     DevBuf<uint64_t> spOff[kSplitSinks];
     DevBuf<uint8_t> spOut[kSplitSinks];
@@ -2767,15 +2772,18 @@ static uint32_t splitSinkMask(uint32_t sinks, bool paired) {
 // The split of a batch's reads, on st: the records' tally zeroed, the size pass, per sink of `mask` the exclusive sums of d.size[s]
 // into off[s][0 .. nQueries]; the sums' totals (tot[s]) and the records (tot[kSplitSinks + s]) fetched and WAITED for; room(tot)
 // then names d.out[s] and d.cap[s], and the write pass is queued behind it.  Blocks of 256 threads.  ev: four events, around the
-// size pass with its sums and around the write pass, or nullptr.  d.nQueries > 0.  (cf_batch_wait_text_split and cf_debug_split)
+// size pass with its sums and around the write pass, or nullptr.  d.nQueries > 0.  sel: the selection of taxa the size pass asks
+// (k_split_sel_size in k_split_size's place: nothing behind the sizes knows of it), or nullptr.  (cf_batch_wait_text_split,
+// cf_debug_split and cf_debug_split_taxa)
 extern "C++" {
 template <typename Room>
-static void enqueueSplit(DTextSplit &d, uint32_t mask, uint64_t *const *off, uint64_t *tileA, uint32_t *tileC, uint64_t *tot, hipEvent_t *ev, hipStream_t st, Room room) {
+static void enqueueSplit(DTextSplit &d, const DTextSplitSel *sel, uint32_t mask, uint64_t *const *off, uint64_t *tileA, uint32_t *tileC, uint64_t *tot, hipEvent_t *ev, hipStream_t st, Room room) {
     const uint64_t nq = d.nQueries;
     const dim3 bl(256), gq((unsigned)((nq + 255) / 256));
     HIP_OK(hipMemsetAsync(d.nRec, 0, kSplitSinks * sizeof(unsigned long long), st));
     if (ev) HIP_OK(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_split_size, gq, bl, 0, st, d);
+    if (sel) hipLaunchKernelGGL(k_split_sel_size, gq, bl, 0, st, d, *sel);
+    else hipLaunchKernelGGL(k_split_size, gq, bl, 0, st, d);
     for (uint32_t s = 0; s < kSplitSinks; s++) {
         if (!(mask >> s & 1u)) continue;
         d.off[s] = off[s];
@@ -2820,6 +2828,9 @@ cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
                 d.size[s] = bt->spSize[s].p; off[s] = bt->spOff[s].p;
             }
             bt->splitMs = 0;
+            // (the classifier's selection as it stands at the batch's first split wait: cf_classifier_set_split_taxa)
+            const bool bySel = cl->splitSel;
+            const DTextSplitSel sel{reinterpret_cast<const TextRow *>(bt->outCompact.p), bt->rowFirst.p, cl->splitMask.p, (uint32_t)cl->ix->h.taxa.size()};
             if (nq) {
                 bt->spRec.ensure(kSplitSinks); bt->hSpTotal.ensure(3 * kSplitSinks);
                 bt->txTileA.ensure(scan_tiles_for(nq) + 1); bt->txTileC.ensure(scan_tiles_for(nq) + 1);
@@ -2828,7 +2839,7 @@ cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
                 uint64_t *const tot = bt->hSpTotal.p;
                 std::memset(tot, 0, 3 * kSplitSinks * 8);
                 uint64_t nMembers[kSplitSinks] = {};
-                enqueueSplit(d, mask, off, bt->txTileA.p, bt->txTileC.p, tot, bt->evSplit, st, [&](const uint64_t *) {
+                enqueueSplit(d, bySel ? &sel : nullptr, mask, off, bt->txTileA.p, bt->txTileC.p, tot, bt->evSplit, st, [&](const uint64_t *) {
                     // the sinks' sizes are known: their room (outside the timed stretches: a buffer that grows is allocated here)
                     for (uint32_t s = 0; s < kSplitSinks; s++) {
                         if (!(mask >> s & 1u)) continue;
@@ -2872,6 +2883,7 @@ cf_status cf_batch_wait_text_split(cf_batch *bt, cf_split_text *out) {
                 bt->splitMs = msA + msB;
             }
             bt->rec.split_sinks = nq ? mask : 0u;
+            bt->splitByTaxa = nq && bySel;
             bt->splitDone = true;
         }
         for (uint32_t s = 0; s < kSplitSinks; s++) {
@@ -2886,6 +2898,44 @@ cf_status cf_batch_split_ms(const cf_batch *bt, float *ms) {
     if (!bt || !ms) return CF_ERR_ARG;
     *ms = bt->splitMs;
     return CF_OK;
+}
+cf_status cf_batch_split_by_taxa(const cf_batch *bt, int32_t *byTaxa) {
+    if (!bt || !byTaxa) return CF_ERR_ARG;
+    if (!bt->splitDone) { g_err = "cf_batch_split_by_taxa: the batch has not been waited for with cf_batch_wait_text_split"; return CF_ERR_ARG; }
+    *byTaxa = bt->splitByTaxa ? 1 : 0;
+    return CF_OK;
+}
+// ---- the selection of taxa a classifier's slots split their reads by: see centrifuge_amd.h
+cf_status cf_split_taxa_mask(const cf_index *ix, const uint64_t *taxids, uint64_t n, uint8_t *mask, uint64_t *nUnknown) {
+    if (!ix || !mask || (n && !taxids)) return CF_ERR_ARG;
+    return guard([&] {
+        cfamd::kreport::Taxonomy tx;
+        tx.quiet = true;
+        tx.load(ix->h, false);
+        std::vector<uint8_t> m;
+        const std::vector<uint64_t> unknown = cfamd::kreport::splitTaxaMask(tx, ix->h.taxa, taxids, n, m);      // (throws on a cycle)
+        std::memcpy(mask, m.data(), m.size());
+        if (nUnknown) *nUnknown = unknown.size();
+    });
+}
+cf_status cf_classifier_set_split_taxa(cf_classifier *cl, const uint64_t *taxids, uint64_t n, uint64_t *nUnknown) {
+    if (!cl || (n && !taxids)) return CF_ERR_ARG;
+    if (nUnknown) *nUnknown = 0;
+    if (cl->ix->device < 0) return CF_ERR_NO_DEVICE;
+    return guard([&] {
+        if (n == 0) { cl->splitSel = false; return; }                      // (the mask stays where it is: a wait that began earlier may read it)
+        const HostIndex &h = cl->ix->h;
+        cfamd::kreport::Taxonomy tx;
+        tx.quiet = true;
+        tx.load(h, false);
+        std::vector<uint8_t> m;
+        const std::vector<uint64_t> unknown = cfamd::kreport::splitTaxaMask(tx, h.taxa, taxids, n, m);
+        HIP_OK(hipSetDevice(cl->ix->device));
+        if (cl->splitMask.n < m.size()) cl->splitMask.alloc(m.size());
+        HIP_OK(hipMemcpy(cl->splitMask.p, m.data(), m.size(), hipMemcpyHostToDevice));
+        cl->splitSel = true;
+        if (nUnknown) *nUnknown = unknown.size();
+    });
 }
 
 cf_status cf_batch_deflate_ms(const cf_batch *bt, float *ms) {
@@ -3635,9 +3685,10 @@ cf_status cf_debug_format(int device, const cf_debug_format_in *in, cf_debug_for
     });
 }
 
-cf_status cf_debug_split(int device, const cf_debug_block *block, uint32_t sinks, cf_debug_split_out *out) {
+// cf_debug_split and, with the rows and the mask of a selection, cf_debug_split_taxa (rows == nullptr: the former)
+static cf_status debugSplit(int device, const cf_debug_block *block, const uint32_t *rows, const uint8_t *selMask, uint32_t nTaxa, uint32_t sinks, cf_debug_split_out *out, const char *who) {
     if (!block || !out) return CF_ERR_ARG;
-    if (sinks & ~(CF_SPLIT_UN | CF_SPLIT_AL)) { g_err = "cf_debug_split: sinks is CF_SPLIT_UN | CF_SPLIT_AL or 0"; return CF_ERR_ARG; }
+    if (sinks & ~(CF_SPLIT_UN | CF_SPLIT_AL)) { g_err = std::string(who) + ": sinks is CF_SPLIT_UN | CF_SPLIT_AL or 0"; return CF_ERR_ARG; }
     const uint32_t mask = splitSinkMask(sinks, block->paired != 0);
     for (uint32_t s = 0; s < kSplitSinks; s++) {
         out->bytes[s] = out->records[s] = 0; out->sized[s] = mask >> s & 1u;
@@ -3649,7 +3700,18 @@ cf_status cf_debug_split(int device, const cf_debug_block *block, uint32_t sinks
         HIP_OK(hipSetDevice(device));
         const uint64_t nq = block->n_queries;
         TapBlock blk;
-        blk.make(*block, "cf_debug_split");
+        blk.make(*block, who);
+        // (a selection: the rows between margins as cf_debug_format lays them, rowFirst as the row stage's scan leaves it, the mask)
+        DevBuf<TextRow> dRows; DevBuf<uint64_t> dRowFirst; DevBuf<uint8_t> dMask;
+        DTextSplitSel sel{};
+        if (rows) {
+            std::vector<uint64_t> rowFirst(nq + 1, 0);
+            for (uint64_t q = 0; q < nq; q++) rowFirst[q + 1] = rowFirst[q] + (block->qinfo[q] & 0x3fu);
+            TapBlock::put(dRows, reinterpret_cast<const TextRow *>(rows), rowFirst[nq], 1, kTapFill);
+            dRowFirst.upload(rowFirst);
+            TapBlock::put(dMask, selMask, (uint64_t)nTaxa + 1, 0, 0);
+            sel = DTextSplitSel{dRows.p, dRowFirst.p, dMask.p, nTaxa};
+        }
         DTextSplit d{};
         d.text = blk.text.p; d.idOff = blk.idOff.p; d.idLen = blk.idLen.p; d.rlen = blk.rlen.p; d.qinfo = blk.qinfo.p;
         d.woff = blk.woff.p; d.bases = blk.bases.p; d.nmask = blk.nmask.p; d.qualOff = block->qual_off ? blk.qualOff.p : nullptr;
@@ -3667,7 +3729,7 @@ cf_status cf_debug_split(int device, const cf_debug_block *block, uint32_t sinks
         tileA.alloc(scan_tiles_for(nq) + 1); tileC.alloc(scan_tiles_for(nq) + 1);
         PinBuf<uint64_t> tot; tot.ensure(2 * kSplitSinks);
         std::memset(tot.p, 0, 2 * kSplitSinks * 8);
-        enqueueSplit(d, mask, off, tileA.p, tileC.p, tot.p, nullptr, nullptr, [&](const uint64_t *) {
+        enqueueSplit(d, rows ? &sel : nullptr, mask, off, tileA.p, tileC.p, tot.p, nullptr, nullptr, [&](const uint64_t *) {
             for (uint32_t s = 0; s < kSplitSinks; s++) if (mask >> s & 1u) { d.out[s] = text[s].p; d.cap[s] = out->cap[s]; }
         });
         HIP_OK(hipDeviceSynchronize());
@@ -3683,6 +3745,13 @@ cf_status cf_debug_split(int device, const cf_debug_block *block, uint32_t sinks
             if (out->cap[s]) HIP_OK(hipMemcpy(out->text[s], text[s].p, out->cap[s], hipMemcpyDeviceToHost));
         }
     });
+}
+cf_status cf_debug_split(int device, const cf_debug_block *block, uint32_t sinks, cf_debug_split_out *out) {
+    return debugSplit(device, block, nullptr, nullptr, 0, sinks, out, "cf_debug_split");
+}
+cf_status cf_debug_split_taxa(int device, const cf_debug_block *block, const uint32_t *rows, const uint8_t *mask, uint32_t n_taxa, uint32_t sinks, cf_debug_split_out *out) {
+    if (!rows || !mask) return CF_ERR_ARG;
+    return debugSplit(device, block, rows, mask, n_taxa, sinks, out, "cf_debug_split_taxa");
 }
 
 static cf_status debugRank(cf_index *ix, const uint8_t *chars, const uint64_t *rows, uint64_t n, uint64_t *out, int g) {

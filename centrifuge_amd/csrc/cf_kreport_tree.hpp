@@ -188,5 +188,41 @@ inline std::vector<uint64_t> lcaTable(const Taxonomy &tx, const std::vector<uint
     return tab;
 }
 
+// --split-taxids: the selection as the read splitter looks it up (split_sel_size_body, cf_textio.hpp), a byte per dense taxon of the
+// index (HostIndex::taxa) and one more behind them for taxID 0 as the one row of a read without an assignment prints it.  A byte is
+// 1 when the taxon or a node of its parent chain — the chain above, the root included — is among `listed`; a taxon the tree lacks
+// (a reference's taxID without a node, taxID 0 itself) has no chain, so only when it is listed itself.  Repeats in the list change
+// nothing, a list that selects nothing is legal.  Returns the listed IDs that are no taxon of the index, each once, in the list's
+// order.  Throws when a chain is longer than kMaxDepth (a cycle), as lcaTable does.
+inline std::vector<uint64_t> splitTaxaMask(const Taxonomy &tx, const std::vector<uint64_t> &taxa, const uint64_t *listed, uint64_t n, std::vector<uint8_t> &mask) {
+    const std::unordered_set<uint64_t> want(listed, listed + n);
+    std::unordered_map<uint64_t, uint8_t> known;                          // tid -> selected, for the nodes a chain has gone through
+    std::vector<uint64_t> chain;
+    mask.assign(taxa.size() + 1, 0);
+    for (size_t i = 0; i < taxa.size(); i++) {
+        chain.clear();
+        uint64_t t = taxa[i];
+        uint8_t sel = 0;
+        for (;;) {
+            auto it = known.find(t);
+            if (it != known.end()) { sel = it->second; break; }
+            if (chain.size() > (size_t)kMaxDepth) throw std::runtime_error(deepMessage());
+            chain.push_back(t);
+            if (want.count(t)) { sel = 1; break; }
+            uint64_t p = 0;
+            if (!tx.parentOf(t, p) || p == t || p == 0) break;            // (no node, a root)
+            t = p;
+        }
+        for (uint64_t c : chain) known[c] = sel;
+        mask[i] = sel;
+    }
+    mask[taxa.size()] = want.count(0) ? 1 : 0;
+    std::vector<uint64_t> unknown;
+    std::unordered_set<uint64_t> seen;
+    for (uint64_t k = 0; k < n; k++)
+        if (!std::binary_search(taxa.begin(), taxa.end(), listed[k]) && seen.insert(listed[k]).second) unknown.push_back(listed[k]);
+    return unknown;
+}
+
 }  // namespace kreport
 }  // namespace cfamd

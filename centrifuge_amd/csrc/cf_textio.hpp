@@ -921,6 +921,40 @@ CF_DEV void split_size_body(const DTextSplit &d, uint32_t q) {
         if (cf_lane() == 0 && v) { cf_atomic_add(&d.nRec[2 * c], v); if (d.paired) cf_atomic_add(&d.nRec[2 * c + 1], v); }
     }
 }
+// ... by a selection of taxa instead (--split-taxids): the class is the ROW's — `al` when the taxon its taxID column prints is
+// selected (mask: a byte per dense taxon and, at nTaxa, taxID 0's, which the one row of a query without rows prints;
+// kreport::splitTaxaMask makes it) —, so a query's max(1, n) records may go a of them to the classified sinks and the others to the
+// unclassified ones.  Only the sizes change.  split_write_body needs no word of this: per sink it takes a query's copies from
+// size[s][q] alone — its loop `c * rec < size` runs size / rec times, rec being the record's bytes it computes from the same idLen
+// and rlen[ra + (s & 1)] as here, never 0 —, asks nothing of qinfo or of a class, and visits every sink that is on for every query;
+// the records of a query are the same bytes, so "in row order" holds whichever of them a sink gets.
+struct DTextSplitSel {
+    const TextRow *rows;                     // the batch's narrow rows and where each query's begin (DTextFmt::rows, rowFirst)
+    const uint64_t *rowFirst;
+    const uint8_t *mask;                     // [nTaxa + 1]
+    uint32_t nTaxa;
+};
+CF_DEV void split_sel_size_body(const DTextSplit &d, const DTextSplitSel &e, uint32_t q) {
+    const bool live = q < d.nQueries;
+    uint32_t un = 0, al = 0;                                                  // the query's records per class (a lane past the end: none)
+    if (live) {
+        const uint32_t n = d.qinfo[q] & 0x3fu, ra = d.paired ? 2 * q : q, idn = d.idLen[ra];
+        if (n) {
+            const uint64_t f0 = e.rowFirst[q];
+            for (uint32_t i = 0; i < n; i++) { const uint32_t t = e.rows[f0 + i].tidx; al += e.mask[t < e.nTaxa ? t : 0u] ? 1u : 0u; }   // (fmt_col_len's t)
+            un = n - al;
+        } else { al = e.mask[e.nTaxa] ? 1u : 0u; un = 1u - al; }
+        for (uint32_t s = 0; s < kSplitSinks; s++)
+            if (split_sink_on(d, s)) d.size[s][q] = ((s >> 1) ? al : un) * (1u + idn + 1u + d.rlen[ra + (s & 1u)] + 3u + d.rlen[ra + (s & 1u)] + 1u);
+    }
+    // the records per class, as split_size_body tallies them: every lane of the wavefront is here
+    for (uint32_t c = 0; c < 2; c++) {
+        if (!split_sink_on(d, 2 * c)) continue;                          // (the same for every thread of the launch)
+        unsigned long long v = c ? al : un;
+        for (int m = CF_WAVE / 2; m > 0; m >>= 1) v += cf_shfl_xor(v, m);
+        if (cf_lane() == 0 && v) { cf_atomic_add(&d.nRec[2 * c], v); if (d.paired) cf_atomic_add(&d.nRec[2 * c + 1], v); }
+    }
+}
 // one record at dst, whose place in the sink is `at` bytes past a dword boundary: every lane of the wavefront, the same arguments
 CF_DEV void split_wave_record(const DTextSplit &d, uint8_t *dst, uint32_t at, uint32_t idOff, uint32_t idn, uint32_t r, uint32_t len, uint32_t lane) {
     const uint64_t wo = d.woff[r];

@@ -482,6 +482,29 @@ cf_status cf_batch_wait_text_split(cf_batch *, cf_split_text *out);
  * k_split_size with the sums per sink, and k_split_write; what lies between them (the host learns the sizes and makes room) and
  * the deflate behind them are not in it */
 cf_status cf_batch_split_ms(const cf_batch *, float *ms);
+/* The same split by a selection of taxa (centrifuge-class --split-taxids).  With a selection in force every PRINTED ROW has a class
+ * of its own: `al` (sinks 2 / 3) when the row's taxID is one of the listed taxa or lies below one of them in the index's taxonomy,
+ * `un` (sinks 0 / 1) otherwise; the one row of a read without an assignment has taxID 0 and is `al` exactly when 0 is listed.  Each
+ * row's record — the bytes described above — goes to the sinks of its row's class, so a read with rows 100, 101, 102 and the
+ * selection {100} puts one record into `al` and two into `un`.  The selection "every taxon but 0" gives the bytes of no selection.
+ * cf_split_taxa_mask (cf_index_open_host is enough) makes the selection's table: mask[i] for dense taxon i (cf_index_taxon_id) is 1
+ * when the taxon or a node of its parent chain in the tree — the chain cf_kreport_enable lays out, the root included — is listed;
+ * a taxID a reference carries but the tree lacks is selected only when it is listed itself; mask[num_taxa] is taxID 0's, as an
+ * unclassified row prints it.  mask has num_taxa + 1 bytes.  *n_unknown (may be NULL): the listed IDs that are no taxon of the
+ * index, each counted once; they select nothing.  Repeats are harmless, a list that selects nothing is legal; a tree with a cycle
+ * is the error cf_kreport_enable gives.
+ * cf_classifier_set_split_taxa builds that table and keeps it on the classifier's device; n == 0 drops the selection.  Like
+ * cf_batch_set_text_split it is read by cf_batch_wait_text_split alone — which then sizes the sinks with k_split_sel_size in
+ * k_split_size's place; the sums, k_split_write, the deflate and cf_launch_record::split_sinks are what they were — and holds for
+ * every batch of the classifier's slots whose FIRST cf_batch_wait_text_split follows the call.  The call does not synchronise with
+ * the slots: changing the selection while a cf_batch_wait_text_split of one of the classifier's slots runs on another thread is the
+ * caller's error.  A classifier without a selection launches what it launched before.  The classification text, the counters and the
+ * Kraken-style tally never depend on it.
+ * cf_batch_split_by_taxa: *by_taxa = 1 when the slot's last cf_batch_wait_text_split sized its batch by a selection, 0 when not
+ * (a batch without queries launches nothing: 0); CF_ERR_ARG before the batch's first split wait. */
+cf_status cf_split_taxa_mask(const cf_index *, const uint64_t *taxids, uint64_t n, uint8_t *mask, uint64_t *n_unknown);
+cf_status cf_classifier_set_split_taxa(cf_classifier *, const uint64_t *taxids, uint64_t n, uint64_t *n_unknown);
+cf_status cf_batch_split_by_taxa(const cf_batch *, int32_t *by_taxa);
 
 /* pinned (page-locked) host memory: what makes the transfers of the async calls truly asynchronous */
 cf_status cf_host_alloc(void **p, size_t bytes);
@@ -731,7 +754,10 @@ cf_status cf_debug_deflate(int device, const void *text, uint64_t n_bytes, uint3
  * query), single (n_taxa + 1 words, the perfect single assignments per dense taxon), tuples (tuples_cap words; the tuples that
  * fit) with *tuple_words the words all tuples need, *total the bytes the size pass summed.  n_queries == 0: nothing is launched.
  * cf_debug_split: sinks (CF_SPLIT_UN | CF_SPLIT_AL) and a room per sink -> per sink its text (cap[s] bytes, 0x5A where nothing was
- * written), the bytes sized, the records and whether it was sized at all. */
+ * written), the bytes sized, the records and whether it was sized at all.
+ * cf_debug_split_taxa: the same with a selection of taxa — rows as cf_debug_format takes them (the query's row count is its qinfo
+ * byte's low six bits) and the mask of cf_split_taxa_mask, n_taxa + 1 bytes — through the same launch code with k_split_sel_size
+ * as the size pass; a row whose dense taxon is not below n_taxa counts as taxon 0, as the formatter prints it. */
 typedef struct {
     const uint8_t  *text;
     uint64_t        text_bytes;
@@ -772,6 +798,8 @@ typedef struct {
 } cf_debug_split_out;
 cf_status cf_debug_format(int device, const cf_debug_format_in *in, cf_debug_format_out *out);
 cf_status cf_debug_split(int device, const cf_debug_block *block, uint32_t sinks, cf_debug_split_out *out);
+cf_status cf_debug_split_taxa(int device, const cf_debug_block *block, const uint32_t *rows, const uint8_t *mask, uint32_t n_taxa,
+                              uint32_t sinks, cf_debug_split_out *out);
 /* random 128-byte-side read bandwidth of the device over the resident sides
  * (the roofline denominator of SURVEY.md §8d): GB/s over `n_loads` loads. */
 cf_status cf_debug_random_read_gbps(cf_index *, uint64_t n_loads, int dependent_steps, double *gbps);
